@@ -2,14 +2,18 @@
 """Headline bench: frames/s of the vszip hot path on MI355X, inputs resident in HBM.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload boxblur|bilateral|ssimulacra2|pipeline]
-                    [--frames F] [--no-cpu] [--no-others]
+                    [--frames F] [--dump-outputs DIR] [--full [--no-cpu] [--no-others]]
 
 Default workload (the JSON line's `value` and `roofline`): vszip.BoxBlur(hradius=vradius=13)
 on 3840x2160 YUV420P16 — the north-star roofline target. A step is one pass of the hot path
 over one batch of F = 64 synthetic frames already resident in HBM (F*3 = 192 planes = one launch).
-The other two headline filters (Bilateral sigmaS=2 sigmaR=2, SSIMULACRA2 ref vs dist) are
-measured in the same run on their BASELINE configs and reported under "others", each beside
-the CPU oracle timed on this box's host cores.
+A plain run sets up, warms up, times the K steps and prints the line: nothing else.
+With --full, the other two headline filters (Bilateral sigmaS=2 sigmaR=2, SSIMULACRA2 ref vs dist)
+are measured in the same run on their BASELINE configs and reported under "others", each beside
+the CPU oracle timed on this box's host cores, together with every side figure of the record
+(CPU baselines, the launch-duration sample, unplaced arenas, the per-clip exchange, PCIe-fed rate).
+--dump-outputs DIR: after the timed steps, what the last step computed goes to DIR/<name>.npy
+(float32 / float64; see dump_planes). The inputs depend on the arguments only.
 N > 1: one process per GPU over RCCL. Either the caller starts the ranks (python -m torch.distributed.run
 ... bench.py --gpus N: RANK / WORLD_SIZE in the environment) or `python bench.py --gpus N` starts them
 itself as CHILD processes before anything in this process has touched the GPU, relays rank 0's line
@@ -455,6 +459,38 @@ def setup_boxblur(dev, rank, frames, radius, tries=None):
     return step, keep
 
 
+# ---------------------------------------------------------------------------
+# --dump-outputs: the arrays a caller of the timed path receives from its last step, so that two builds can be
+# compared output for output on identical inputs. A batch of planes is written as its first frame in full plus a
+# fixed, seeded sample of every plane of the batch; together under 64 MB at every --frames (4K: 49.8 + <= 12 MB).
+# ---------------------------------------------------------------------------
+DUMP_FULL_BYTES = 52_000_000
+DUMP_SAMPLE_BYTES = 12_000_000
+
+
+def dump_planes(dev, planes, name: str, frame_planes: int = 3) -> dict:
+    """{<name>_frame0_p<k>: plane k of the first frame, <name>_sample: [plane, i] at seeded positions}, float32"""
+    n = max(1, min(8192, DUMP_SAMPLE_BYTES // 4 // len(planes)))
+    rng = np.random.default_rng(0x5A17)
+    out, sample, full_bytes = {}, np.empty((len(planes), n), np.float32), 0
+    for k, p in enumerate(planes):
+        a = dev.download(p)
+        if k < frame_planes and full_bytes + 4 * a.size <= DUMP_FULL_BYTES:
+            out[f"{name}_frame0_p{k}"] = a.astype(np.float32)
+            full_bytes += 4 * a.size
+        sample[k] = a.reshape(-1)[rng.integers(0, a.size, n)]
+    out[f"{name}_sample"] = sample
+    return out
+
+
+def write_outputs(dirname: str, arrays: dict) -> None:
+    d = Path(dirname)
+    d.mkdir(parents=True, exist_ok=True)
+    for k, v in arrays.items():
+        v = np.asarray(v)
+        np.save(d / f"{k}.npy", v if v.dtype in (np.float32, np.float64) else v.astype(np.float64))
+
+
 def setup_bilateral(dev, w, h, frames, sigma_s=2, sigma_r=2, eight_bit=False):
     base = natural_frame(w, h)
     if eight_bit:  # YUV420P8: the picture's own 8-bit samples
@@ -568,9 +604,12 @@ def setup_pipeline(dev, w, h, frames):
     return step, (srcs, mid, outp, cfg), scores
 
 
-def pipeline_line(dev, timed, world, frames, steps, warmup, max_over_ranks, reduce_scalars):
+def pipeline_line(dev, timed, world, frames, steps, warmup, max_over_ranks, reduce_scalars, outputs=None):
+    """outputs (a dict, or None): receives the last step's per-frame scores (--dump-outputs)"""
     step, keep, scores = setup_pipeline(dev, W8K, H8K, frames)
     dt, region_ms, _, _ = timed.run(step, steps, warmup)
+    if outputs is not None:
+        outputs["pipeline_scores"] = np.asarray(scores, np.float64)
     dt = max_over_ranks(dt)
     frame_bytes = 3 * W8K * H8K * 4  # 398 131 200
     # compulsory traffic per frame: source read by Bilateral and by SSIMULACRA2, the two intermediates written and read once
@@ -1363,15 +1402,17 @@ def plugin_legs_child():
 def main() -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=2000, help="timed steps (default: ~1.2 s of BoxBlur launches)")
+    ap.add_argument("--steps", type=int, default=None, help="timed steps (default: 2000 BoxBlur steps, ~1.2 s of launches; 50 of the other workloads)")
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--frames", type=int, default=64, help="frames per step per GPU (64 4K YUV420P16 frames = 192 planes = one BoxBlur launch)")
     ap.add_argument("--workload", default="boxblur", choices=["boxblur", "bilateral", "ssimulacra2", "pipeline"])
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-others", action="store_true")
-    ap.add_argument("--exchange-only", action="store_true", help="--no-cpu --no-others, but the per-clip exchange step (XPSNR accumulators over the collective backend) still runs: the RCCL smoke test")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed to DIR/<name>.npy (float32 / float64)")
+    ap.add_argument("--full", action="store_true", help="besides the headline: CPU baselines, the other legs and every side figure of the record")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: no CPU baselines")
+    ap.add_argument("--no-others", action="store_true", help="with --full: no other legs")
+    ap.add_argument("--exchange-only", action="store_true", help="--full --no-cpu --no-others, but the per-clip exchange step (XPSNR accumulators over the collective backend) still runs: the RCCL smoke test")
     ap.add_argument("--radius", type=int, default=RADIUS, help="development: BoxBlur radius (headline = 13)")
-    ap.add_argument("--min-seconds", type=float, default=1.0, help="kernel time of the launch-duration sample (roofline.launch_us)")
+    ap.add_argument("--min-seconds", type=float, default=1.0, help="with --full: kernel time of the launch-duration sample (roofline.launch_us)")
     ap.add_argument("--dry-launch", action="store_true", help="with --gpus N > 1: print the rank-launch command and exit (no GPU)")
     ap.add_argument("--plugin-legs-only", action="store_true", help="internal: run the legs through libvszip.so and print their records as one JSON line (see plugin_child below)")
     a = ap.parse_args()
@@ -1383,12 +1424,12 @@ def main() -> int:
         out_fd.flush()
         return 0
     if a.exchange_only:
-        a.no_cpu = a.no_others = True
+        a.full = a.no_cpu = a.no_others = True
 
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return launch_ranks(a, [x for x in sys.argv[1:] if x != "--dry-launch"])
-    if a.workload != "boxblur" and a.steps == 2000:
-        a.steps = 50  # the other workloads' steps are milliseconds, not 0.6 ms
+    if a.steps is None:
+        a.steps = 2000 if a.workload == "boxblur" else 50  # the other workloads' steps are milliseconds, not 0.6 ms
 
     # stdout carries exactly ONE line, the JSON. Libraries that print to fd 1 (RCCL's version banner
     # does) are sent to stderr for the lifetime of the process; the JSON goes to the saved fd.
@@ -1449,9 +1490,10 @@ def main() -> int:
 
     F = a.frames
     out = None
+    dump = {} if (a.dump_outputs and rank == 0) else None  # name -> array of the last timed step
     if a.workload == "pipeline":
         nf = max(1, min(F // 16, 8))  # 64 -> 4 frames of 398 MB per step per GPU
-        res = pipeline_line(dev, timed, world, nf, a.steps, a.warmup, max_over_ranks, reduce_scalars)
+        res = pipeline_line(dev, timed, world, nf, a.steps, a.warmup, max_over_ranks, reduce_scalars, dump)
         out = {"metric": "frames/sec: Bilateral->BoxBlur->SSIMULACRA2 pipeline 7680x4320 RGBS", "value": res.pop("value"), "unit": res.pop("unit"),
                "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": res.pop("ms_per_step"), "higher_is_better": True,
                "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
@@ -1461,6 +1503,8 @@ def main() -> int:
     elif a.workload == "boxblur":
         step, keep = setup_boxblur(dev, rank, F, a.radius)
         dt, region_ms, dom_ms, launches = timed.run(step, a.steps, a.warmup)
+        if dump is not None:
+            dump.update(dump_planes(dev, keep[1].planes, "boxblur_dst"))
         dt = max_over_ranks(dt)
         frame_bytes = sum(2 * s[0] * s[1] for s in yuv420_shapes(W4K, H4K))  # 24 883 200
         alg_bytes = 2 * frame_bytes * F * a.steps / launches   # per ring-kernel launch: every pixel read once + written once
@@ -1508,7 +1552,8 @@ def main() -> int:
             out["roofline"]["rocprof_source"] = f"profiles/{prof[2]} ({prof[1]} calls; replayed)"
         out["roofline"]["traffic_source"] = ("replayed from the committed PMC passes of this command (profiles/r*_boxblur_pmc.json), not measured in this run"
                                              if out["roofline"]["traffic"] is not None else None)
-        if rank == 0:
+        # Everything below up to the end of this branch is --full only: side figures that take runs of their own.
+        if rank == 0 and a.full:
             st_ = timed.launch_stats(step, a.min_seconds)
             if st_:
                 out["roofline"]["launch_us"] = st_
@@ -1517,16 +1562,17 @@ def main() -> int:
         # Outside the timed region: the one collective of the design — a per-clip scalar (here the
         # mean luma of the blurred clip, PlaneAverage over every rank's frames) all-reduced over
         # RCCL, like XPSNR's / SSIMULACRA2's per-clip sums (vszip_amd.cluster).
-        try:
-            luma = keep[1].planes[0::3]
-            avgs, _ = dev.plane_average(luma[:48], exclude=[-1])
-            tot = vszip_amd.cluster.allreduce_clip_scalars(np.array([float(np.sum(avgs)), float(len(avgs))]), device=coll_dev)
-            out["config"]["clip_mean_luma"] = {"value": float(tot[0] / tot[1]), "frames": int(tot[1]), "reduced_over_ranks": world}
-        except Exception as e:  # informative only
-            out["config"]["clip_mean_luma"] = {"error": str(e)}
+        if a.full:
+            try:
+                luma = keep[1].planes[0::3]
+                avgs, _ = dev.plane_average(luma[:48], exclude=[-1])
+                tot = vszip_amd.cluster.allreduce_clip_scalars(np.array([float(np.sum(avgs)), float(len(avgs))]), device=coll_dev)
+                out["config"]["clip_mean_luma"] = {"value": float(tot[0] / tot[1]), "frames": int(tot[1]), "reduced_over_ranks": world}
+            except Exception as e:  # informative only
+                out["config"]["clip_mean_luma"] = {"error": str(e)}
         del keep
         # Side scalar only (never `value`): the same launch on arenas the allocator did NOT place (VSZIP_PLACEMENT=0: plain hipMalloc)
-        if rank == 0 and world == 1 and not a.no_others and a.radius == RADIUS:
+        if a.full and rank == 0 and world == 1 and not a.no_others and a.radius == RADIUS:
             try:
                 with dev.options(VSZIP_PLACEMENT=0):
                     step_p, keep_p = setup_boxblur(dev, rank, F, a.radius)
@@ -1538,13 +1584,13 @@ def main() -> int:
                 out["config"]["unplaced_error"] = str(e)[:100]
         # The exchange step on real data: XPSNR's per-clip accumulators over RCCL (all ranks take part)
         try:
-            if not a.no_others or a.exchange_only:
+            if a.full and (not a.no_others or a.exchange_only):
                 out["config"]["xpsnr_clip"] = xpsnr_clip_leg(dev, vszip_amd, rank, world, coll_dev)
         except Exception as e:
             out["config"]["xpsnr_clip"] = {"error": str(e)}
         # PCIe-fed rate at this N: every rank feeds its GPU from pinned host frames at the same time
         try:
-            if a.no_others:
+            if a.no_others or not a.full:
                 raise KeyboardInterrupt
             pc = pcie_boxblur(vszip_amd, local_rank, a.radius, barrier=barrier)
             dt_p = max_over_ranks(pc["seconds"])
@@ -1557,9 +1603,9 @@ def main() -> int:
             pass
         except Exception as e:
             out["config"]["pcie_fed"] = {"error": str(e)}
-        if rank == 0 and world == 1 and not a.no_cpu:
+        if a.full and rank == 0 and world == 1 and not a.no_cpu:
             out["cpu_baseline"] = cpu_boxblur()
-        if world == 1 and not a.no_others:
+        if a.full and world == 1 and not a.no_others:
             others = {}
             for name, (w, h, nf) in {"bilateral_1080p": (W1080, H1080, 64), "bilateral_4k": (W4K, H4K, 16)}.items():
                 st, keep = setup_bilateral(dev, w, h, nf)
@@ -1684,11 +1730,16 @@ def main() -> int:
                "config": {"workload": "vszip.Bilateral sigmaS=2 sigmaR=2, 1920x1080 YUV420P16, natural content tiled", "frames_per_step_per_gpu": F},
                "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": None,
                             "kernel": "bilateral_walk16_kernel<3,2> luma + <2,1> chroma (column-walking waves, exact range LUT packed in LDS)"}}
-        if rank == 0 and world == 1 and not a.no_cpu:
+        if dump is not None:
+            dump.update(dump_planes(dev, keep[1], "bilateral_dst"))
+        if a.full and rank == 0 and world == 1 and not a.no_cpu:
             out["cpu_baseline"] = cpu_bilateral(W1080, H1080)
     else:
         pairs = max(1, F // 4)
         step, keep = setup_ssimulacra2(dev, W4K, H4K, pairs)
+        if dump is not None:  # the call returns the scores: keep the last step's
+            call = step
+            step = lambda: dump.__setitem__("ssimulacra2_scores", np.asarray(call(), np.float64))
         dt, kernel_ms, _, _ = timed.run(step, a.steps, a.warmup)
         dt = max_over_ranks(dt)
         avg_s = kernel_ms * 1e-3 / a.steps  # whole pipeline (6 scales x {xyb/downscale, maps} + final), not one kernel
@@ -1699,9 +1750,11 @@ def main() -> int:
                "config": {"workload": "vszip.SSIMULACRA2 ref vs dist, 3840x2160 RGBS linear", "pairs_per_step_per_gpu": pairs},
                "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": None,
                             "kernel": "whole SSIMULACRA2 pipeline (ssim_pyr: scales 0+1 in one pass over the source; ssim_xyb_down x3, ssim_maps x5, ssim_final); algorithmic bytes = the two input frames"}}
-        if rank == 0 and world == 1 and not a.no_cpu:
+        if a.full and rank == 0 and world == 1 and not a.no_cpu:
             out["cpu_baseline"] = cpu_ssimulacra2(W4K, H4K)
 
+    if dump is not None:
+        write_outputs(a.dump_outputs, dump)
     if rank == 0:
         out["config"]["timed_calls"] = getattr(timed, "calls", 0) + UNTIMED_CALLS
         out["config"]["barrier_ms"] = getattr(timed, "barrier_ms", None)  # one barrier (all ranks + device sync) as timed before the last timed region  # calls of the workload's step in this process (tools/summarize_prof.py: launches per call)

@@ -156,3 +156,30 @@ def test_cpu_record_carries_threads_single_thread_rate_and_scaling(monkeypatch):
     leg = bench.compact_leg({"value": 1000.0, "unit": "frames/s", "cpu_baseline": rec})
     assert set(leg["cpu"]) == {"value", "cores", "x", "single", "scaling"}
     assert math.isclose(leg["cpu"]["x"], 1000.0 / rec["value"], rel_tol=1e-9)
+
+
+def test_dumped_outputs_are_float_bounded_and_the_same_every_run(tmp_path):
+    """--dump-outputs: the first frame in full plus a seeded sample of every plane, float32 / float64, under 64 MB for the
+    headline's 64 4K YUV420P16 frames and for four times as many; the same positions on every run"""
+    import numpy as np
+
+    class HostDev:  # download() of a plane that is already on the host
+        def download(self, p):
+            return p
+
+    shapes = bench.yuv420_shapes(bench.W4K, bench.H4K)
+    for frames in (64, 256):
+        planes = [np.full(s, 3 * f + k, np.uint16) for f in range(frames) for k, s in enumerate(shapes)]
+        d = bench.dump_planes(HostDev(), planes, "boxblur_dst")
+        assert sum(v.nbytes for v in d.values()) < 64e6
+        assert all(v.dtype == np.float32 for v in d.values())
+        assert [d[f"boxblur_dst_frame0_p{k}"].shape for k in range(3)] == shapes
+        s = d["boxblur_dst_sample"]
+        assert s.shape[0] == 3 * frames and np.array_equal(s, np.arange(3 * frames, dtype=np.float32)[:, None] * np.ones_like(s))
+    ramp = [np.arange(s[0] * s[1], dtype=np.uint16).reshape(s) for s in shapes]
+    d1, d2 = bench.dump_planes(HostDev(), ramp, "x"), bench.dump_planes(HostDev(), ramp, "x")
+    assert np.array_equal(d1["x_sample"], d2["x_sample"])
+    bench.write_outputs(tmp_path / "out", dict(d1, scores=np.array([1, 2], np.int64)))
+    assert sorted(p.name for p in (tmp_path / "out").iterdir()) == ["scores.npy", "x_frame0_p0.npy", "x_frame0_p1.npy", "x_frame0_p2.npy", "x_sample.npy"]
+    assert np.load(tmp_path / "out" / "scores.npy").dtype == np.float64
+    assert np.array_equal(np.load(tmp_path / "out" / "x_sample.npy"), d1["x_sample"])

@@ -27,7 +27,7 @@ def test_one_rank_over_a_real_nccl_group(tmp_path):
     env = dict(os.environ, VSZIP_BENCH_FORCE_DIST="1", VSZIP_BENCH_DETAIL=str(tmp_path / "detail.json"), MASTER_ADDR="127.0.0.1")
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=1", "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
-           str(ROOT / "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--exchange-only"]
+           str(ROOT / "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--full", "--exchange-only"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=str(ROOT))
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

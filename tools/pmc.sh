@@ -8,7 +8,7 @@ rm -rf $out; mkdir -p $out
 n=0
 for set in "$@"; do
   n=$((n+1))
-  rocprofv3 --pmc $set --output-format csv -d $out/set$n -- python3 $R/bench.py --no-cpu --no-others --steps 4 --warmup 1 $BENCH_ARGS > /dev/null 2> $out/set$n.err
+  rocprofv3 --pmc $set --output-format csv -d $out/set$n -- python3 $R/bench.py --full --no-cpu --no-others --steps 4 --warmup 1 $BENCH_ARGS > /dev/null 2> $out/set$n.err
 done
 python3 - <<PY
 import csv, glob, collections

@@ -19,7 +19,7 @@ prof() {
 }
 only=${ONLY:-boxblur bilateral ssimulacra2 legs}
 want() { case " $only " in *" $1 "*) return 0;; esac; return 1; }
-want boxblur && prof ${rt}_boxblur $R/bench.py --no-cpu --no-others --steps 50 --warmup 3 --min-seconds 0.1
+want boxblur && prof ${rt}_boxblur $R/bench.py --full --no-cpu --no-others --steps 50 --warmup 3 --min-seconds 0.1
 want bilateral && prof ${rt}_bilateral $R/bench.py --no-cpu --no-others --workload bilateral --steps 10 --warmup 2
 want ssimulacra2 && prof ${rt}_ssimulacra2 $R/bench.py --no-cpu --no-others --workload ssimulacra2 --steps 5 --warmup 1
 want legs && prof ${rt}_legs $R/tools/prof_legs.py eedi3 xpsnr boxblur_other planestats ssim_yuv
