@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define VSZIP_ABI_VERSION 4 /* 4 (round 5): vszip_dev_alloc searches a bounded number of candidates and keeps nothing (below); vszip_dev_arena_info added; vszip_dev_trim, vszip_dev_placement_info and
+#define VSZIP_ABI_VERSION 4 /* additive since 4: vszip_clahe; 4 (round 5): vszip_dev_alloc searches a bounded number of candidates and keeps nothing (below); vszip_dev_arena_info added; vszip_dev_trim, vszip_dev_placement_info and
                                vszip_dev_alloc_probed removed (nothing is searched for or parked any more); 3 (round 4): vszip_ctx_set_option / _get_option, vszip_dev_probe_region,
                                vszip_plane_average_async, vszip_plane_minmax_async added; 2 (round 3): vszip_ssim_source grew (YUV sources); entry points added since 1:
                                vszip_chain_run, vszip_ssimulacra2_src, vszip_to_rgbs_linear, vszip_probe_read_each, vszip_resample_table */
@@ -187,6 +187,18 @@ int vszip_limit_filter(vszip_ctx *ctx, int dtype, const vszip_plane *planes, con
  * :96-99), else 0. planes[i].src is `clip`'s plane, planes[i].ref `clip2`'s. Asynchronous.
  */
 int vszip_adaptive_binarize(vszip_ctx *ctx, const vszip_plane *planes, int nplanes, int c);
+
+/*
+ * CLAHE — replaces filter.applyCLAHE (src/filters/clahe.zig:14-38: calcLut :40-156, interpolate :176-282) as called per plane by
+ * CLAHE(T).getFrame (src/vapoursynth/clahe.zig:23-49). dtype VSZIP_U8 or VSZIP_U16; every plane equalised with its own size; dst may equal src.
+ * Asynchronous on the context stream.
+ * Any number of planes of any sizes (the planes of many frames) in one call; `limit` and tiles_x / tiles_y are the wrapper's
+ * d.limit and d.tiles. VSZIP_ERR_ARG, each with its own vszip_last_error text, for the wrapper's create-time checks
+ * (clahe.zig(vs):70-112) applied to every plane of the table: a dtype other than U8 / U16, tiles_x or tiles_y < 1, a tile
+ * count above a plane's width or height, limit * tile area / hist_size above INT32_MAX. Histograms and LUTs live in the
+ * context's scratch (grow-only), at most VSZIP_CLAHE_SCRATCH_MIB of it per plane group (csrc/options.inc).
+ */
+int vszip_clahe(vszip_ctx *ctx, int dtype, const vszip_plane *planes, int nplanes, uint32_t limit, int tiles_x, int tiles_y);
 
 /*
  * PlaneMinMax — replaces filter.minMax / minMaxRef / minMaxNoThr / minMaxNoThrRef

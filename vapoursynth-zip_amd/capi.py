@@ -119,6 +119,7 @@ SYMBOLS = {
     "vszip_limiter": (_i, [_vp, _i, _PP, _i, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "vszip_limit_filter": (_i, [_vp, _i, _PP, C.POINTER(_vp), C.POINTER(_pd), _i, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "vszip_adaptive_binarize": (_i, [_vp, _PP, _i, _i]),
+    "vszip_clahe": (_i, [_vp, _i, _PP, _i, C.c_uint32, _i, _i]),
     "vszip_plane_average": (_i, [_vp, _i, _PP, _i, C.POINTER(C.c_int32), _i, _i, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "vszip_plane_minmax": (_i, [_vp, _i, _PP, _i, C.c_float, C.c_float, _i, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "vszip_plane_average_async": (_i, [_vp, _i, _PP, _i, C.POINTER(C.c_int32), _i, _i, _vp]),
@@ -437,6 +438,28 @@ class Device:
         los, his = (C.c_double * n)(*[float(v) for v in lo]), (C.c_double * n)(*[float(v) for v in hi])
         dt, fn, ctx, check = _NP2DT[srcs[0].dtype], self.lib.vszip_limiter, self.ctx, self.check
         return lambda: check(fn(ctx, dt, table, n, los, his))
+
+    @staticmethod
+    def clahe_tiles(tiles) -> tuple:
+        """the wrapper's `tiles` argument (src/vapoursynth/clahe.zig:76-91): an int, [n] or [x, y] -> (tiles_x, tiles_y)"""
+        t = [int(tiles)] if isinstance(tiles, (int, np.integer)) else [int(v) for v in tiles]
+        if len(t) < 1 or len(t) > 2:
+            raise ValueError("CLAHE : tiles array can't have more than 2 values.")
+        return (t[0], t[1] if len(t) == 2 else t[0])
+
+    def clahe(self, srcs, dsts, limit=7, tiles=3):
+        """vszip.CLAHE on every plane of srcs (8- or 16-bit, any sizes; dsts may be srcs): limit, tiles as the reference's defaults."""
+        tx, ty = self.clahe_tiles(tiles)
+        table = self.plane_table(srcs, dsts)
+        self.check(self.lib.vszip_clahe(self.ctx, _NP2DT[srcs[0].dtype], table, len(srcs), int(limit), tx, ty))
+
+    def prepared_clahe(self, srcs, dsts, limit=7, tiles=3):
+        """-> a callable queueing vszip_clahe on argument blocks built once."""
+        tx, ty = self.clahe_tiles(tiles)
+        n = len(srcs)
+        table = self.plane_table(srcs, dsts)
+        dt, fn, ctx, check, lim = _NP2DT[srcs[0].dtype], self.lib.vszip_clahe, self.ctx, self.check, int(limit)
+        return lambda: check(fn(ctx, dt, table, n, lim, tx, ty))
 
     def prepared_limit_filter(self, flts, srcs, dsts, dark_thr, bright_thr, elast):
         """-> a callable queueing vszip_limit_filter (no third clip) on argument blocks built once."""

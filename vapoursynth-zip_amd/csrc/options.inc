@@ -17,6 +17,7 @@ VSZIP_OPT(placement, "VSZIP_PLACEMENT", 1)                // large vszip_dev_all
 VSZIP_OPT(placement_min_mib, "VSZIP_PLACEMENT_MIN_MIB", 256)    // ... from this size on
 VSZIP_OPT(placement_tries, "VSZIP_PLACEMENT_TRIES", 24)         // ... looking at no more candidates than this (and never holding more than a quarter of the free device memory)
 VSZIP_OPT(placement_budget_ms, "VSZIP_PLACEMENT_BUDGET_MS", 300)  // ... and never starting another candidate after this many milliseconds of search
+VSZIP_OPT(clahe_scratch_mib, "VSZIP_CLAHE_SCRATCH_MIB", 1024)  // CLAHE: histogram + LUT storage of one plane group at most (a larger table runs in several groups; a plane is never split)
 
 // ---- path selectors between shipped kernels ----
 VSZIP_OPT(scan_mode, "VSZIP_SCAN_MODE", 0)                // BoxBlur CT: 0 ring kernel, 1 generic kernel + shuffle scan, 2 generic kernel + DPP scan
