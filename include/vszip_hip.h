@@ -114,7 +114,39 @@ int vszip_probe_read(vszip_ctx *ctx, double *total_ms, int *launches);
 /* the same, also copying the first `cap` launch durations (ms, launch order) to each_ms */
 int vszip_probe_read_each(vszip_ctx *ctx, double *total_ms, int *launches, float *each_ms, int cap);
 
-/* One plane of one frame. Strides in elements of the sample type. */
+/* One plane of one frame. Strides in elements of the sample type.
+ *
+ * Plane memory: what a call reads and writes. Valid for every entry point that takes planes: the vszip_plane table calls
+ * and the pointer-array calls (vszip_ssimulacra2 / _src, vszip_to_rgbs_linear, vszip_xpsnr_wsse / _batch, the sclips /
+ * mclips of vszip_eedi3 / _mclip, vszip_limit_filter's refs, vszip_adaptive_binarize's second clip in `ref`). A plane is
+ * (pointer, stride, w, h) with stride >= w. Derived from the kernels ("Furthest read of every
+ * kernel") and kept by tests/test_gpu_footprint.py.
+ *
+ * 1. Readable extent. For every INPUT plane the caller provides h x stride samples of mapped device memory from the
+ *    plane pointer: the pitch padding [w, stride) of every row, the last row's included. Vector paths load whole
+ *    16-byte lane groups and may read padding (never beyond h x stride; what they read there is masked out, clause 2).
+ *    Nothing before the plane pointer is read. For every OUTPUT plane the caller owns h x stride samples likewise (the
+ *    ring kernels' store descriptors are bounded by that product), although only clause 3's samples are written.
+ * 2. Independence. No output sample, returned scalar or error code depends on any byte outside [0, w) x h of the input
+ *    planes: not on pitch padding, not on memory between or around planes. Inside [0, w) x h every sample is an input,
+ *    with one exception: vszip_eedi3 / _mclip with dh = 0 and horizontal = 0 never read the source rows of parity `field`
+ *    (those are the rows the call interpolates; planes[i].src has the full height h, of which rows field, field + 2, ...
+ *    may hold anything).
+ * 3. Written extent. Input planes are never written. Of an output plane a call writes [0, w) of each of its h rows and
+ *    nothing else: no pitch padding, no byte before the plane, none after column w - 1 of row h - 1. This holds on
+ *    every path, the 16-byte vector paths included (their last lane group is masked or finished by scalar stores); a
+ *    window into a larger picture keeps its neighbours.
+ * 4. Base alignment and aliasing. Every base alignment of the sample type and every stride >= w are accepted. The fast
+ *    paths need plane pointers and row pitches (in bytes) that are multiples of 16 (what hipMalloc and VapourSynth
+ *    frames give); anything else takes a slower kernel with the same results, bit for bit. One combination is refused
+ *    instead of served: a horizontal pass of vszip_boxblur's run-time-radius integer path over rows longer than 16000
+ *    samples needs 16-byte aligned planes (VSZIP_ERR_UNSUPPORTED). Nothing is ever silently wrong for an alignment.
+ *    dst == src (same pointer, same stride) is allowed for the point filters vszip_limiter, vszip_limit_filter (dst may
+ *    be the flt plane, the source plane or refs[i]) and vszip_adaptive_binarize (dst may be either clip), whose every
+ *    output sample depends on the input samples at the same position only, and for vszip_clahe (the histograms are
+ *    complete before the first store). Every other filter reads neighbourhoods: dst must not overlap any input, and
+ *    two output planes of one call must not overlap each other. Partial overlap is never allowed.
+ */
 typedef struct vszip_plane {
     const void *src; /* input plane */
     void *dst;       /* output plane (filters that write pixels) */
@@ -343,7 +375,9 @@ int vszip_resample_table(int src_dim, int dst_dim, double shift, int32_t *left, 
  * the transposes of :220-246. 32-bit float planes only (createImpl :316-319).
  * planes[i].src is src_w x src_h; planes[i].dst is src_w x (dh ? 2*src_h : src_h) for EEDI3 and
  * (dh ? 2*src_w : src_w) x src_h for EEDI3H. `field` is the frame's resolved parity 0/1
- * (getFrame :166-172 folds _FieldBased and field 2/3 into it). sclips[i] (may be NULL, as may
+ * (getFrame :166-172 folds _FieldBased and field 2/3 into it). With dh = 0 the source rows (EEDI3H:
+ * columns) of parity `field` are replaced by the interpolation; the vertical form does not read them at all
+ * ("Plane memory", clause 2), so a host need not upload them. sclips[i] (may be NULL, as may
  * the array) has dst's geometry. Parameters are the user-level ones (defaults: alpha .2,
  * beta .25, gamma 20, nrad 2, mdis 20, hp 0, vcheck 2, vthresh 32/64/4); the scaling of
  * :465-473 happens inside. Errors mirror createImpl's messages.

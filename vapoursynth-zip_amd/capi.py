@@ -321,6 +321,9 @@ class Device:
         dtype = np.dtype(dtype)
         stride = -(-w // align_elems) * align_elems
         p = C.c_void_p()
+        # The + 256 is slack behind the last row that dates from the first kernel commit: a read that ran up to 256 bytes past a plane would land in it
+        # unseen. It is not part of the contract (include/vszip_hip.h, "Plane memory": a caller owns h x stride samples and no more) and nothing may
+        # rely on it; what keeps kernels inside their planes is tests/test_gpu_footprint.py, whose planes do not come from here (tests/guarded.py).
         self.check(self.lib.vszip_dev_alloc(self.ctx, stride * h * dtype.itemsize + 256, C.byref(p)))
         return DevPlane(self, p.value, w, h, stride, dtype)
 
@@ -623,14 +626,20 @@ class Device:
         """One frame's source planes -> [R, G, B] linear-light f32 DevPlanes (hz.toRGBS + sRGBtoLinearRGB)."""
         p0 = planes[0]
         dst = [self.empty(p0.h, p0.w, np.float32) for _ in range(3)]
+        self.to_rgbs_linear_into(fmt, planes, dst)
+        self.sync()
+        return dst
+
+    def to_rgbs_linear_into(self, fmt: SsimSource, planes, dst):
+        """to_rgbs_linear() into three f32 planes the caller brings (one pitch); asynchronous"""
+        p0 = planes[0]
         per = 1 if fmt.family == CF_GRAY else 3
         s = (C.c_void_p * per)(*[p.ptr for p in planes[:per]])
         d = (C.c_void_p * 3)(*[p.ptr for p in dst])
+        assert dst[0].stride == dst[1].stride == dst[2].stride
         if fmt.family == CF_YUV:
             fmt.chroma_stride = planes[1].stride
         self.check(self.lib.vszip_to_rgbs_linear(self.ctx, C.byref(fmt), s, p0.stride, d, dst[0].stride, p0.w, p0.h))
-        self.sync()
-        return dst
 
     def eedi3(self, srcs, field, dh=False, alpha=0.2, beta=0.25, gamma=20.0, nrad=2, mdis=20, hp=False, vcheck=2,
               vthresh0=32.0, vthresh1=64.0, vthresh2=4.0, sclips=None, horizontal=False, mclips=None):
@@ -641,6 +650,12 @@ class Device:
                 dsts.append(self.empty(s.h, s.w * 2 if dh else s.w, np.float32))
             else:
                 dsts.append(self.empty(s.h * 2 if dh else s.h, s.w, np.float32))
+        self.eedi3_into(srcs, dsts, field, dh, alpha, beta, gamma, nrad, mdis, hp, vcheck, vthresh0, vthresh1, vthresh2, sclips, horizontal, mclips)
+        return dsts
+
+    def eedi3_into(self, srcs, dsts, field, dh=False, alpha=0.2, beta=0.25, gamma=20.0, nrad=2, mdis=20, hp=False, vcheck=2,
+                   vthresh0=32.0, vthresh1=64.0, vthresh2=4.0, sclips=None, horizontal=False, mclips=None):
+        """eedi3() on output planes the caller brings (dsts[i]: the geometry vszip_eedi3 states for planes[i].dst)."""
         n = len(srcs)
         table = self.plane_table(srcs, dsts)
         prm = Eedi3Params(int(dh), alpha, beta, gamma, nrad, mdis, int(hp), vcheck, vthresh0, vthresh1, vthresh2)
@@ -655,7 +670,6 @@ class Device:
             self.check(self.lib.vszip_eedi3_mclip(self.ctx, table, sp, ss, mp, ms, n, field, int(horizontal), C.byref(prm)))
         else:
             self.check(self.lib.vszip_eedi3(self.ctx, table, sp, ss, n, field, int(horizontal), C.byref(prm)))
-        return dsts
 
     def xpsnr_wsse(self, org, rec, prev1=None, prev2=None, depth=8, frame_rate=24, temporal=True):
         """org / rec: lists of 1 or 3 DevPlanes (u8/u16). -> [wsse64 per plane]"""
