@@ -25,7 +25,9 @@ FLAGS = [
 ]
 # per-source flags. eedi3: the SLP vectoriser pairs the line kernel's f32 adds into v_pk_add_f32, which on gfx950's 32-lane SIMDs saves no cycles,
 # and pays for the pairs with register copies (measured: +1.7 % with it off, profiles/r04_notes.md section 10)
-FILE_FLAGS = {"eedi3": ["-fno-slp-vectorize"]}
+# limit_filter: the vector-combine pass turns the 8-bit kernel's 16-byte loads into byte loads (their lanes are only extracted), and those lose
+# the non-temporal hint before the backend merges them back into 16-byte loads (tests/test_stream_cache_hints.py)
+FILE_FLAGS = {"eedi3": ["-fno-slp-vectorize"], "limit_filter": ["-mllvm", "-disable-vector-combine"]}
 
 
 def _stale(out: Path, deps) -> bool:

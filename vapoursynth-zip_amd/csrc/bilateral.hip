@@ -29,11 +29,9 @@
 #include <type_traits>
 #include <vector>
 
-#include "common.hpp"
+#include "plane_table.hpp"
 
 namespace {
-
-constexpr int kMaxPlanesBL = 192;  // planes per launch (64 YUV frames): the persistent kernels pay their table load and their tail once per launch
 
 struct BLPlane {
     const void *src, *ref;
@@ -46,7 +44,7 @@ struct BLPlane {
 };
 
 struct BLParams {
-    BLPlane p[kMaxPlanesBL];
+    BLPlane p[kPlanesPerLaunch];
     int nplanes;
     float peak;
     int lut_len, lut_offset;  // tiled kernel with the range LUT in LDS: entries, byte offset behind the tiles
@@ -97,12 +95,8 @@ template <typename T, bool JOINT, bool LDSLUT>
 __global__ __launch_bounds__(kBX *kBY) void bilateral_tiled_kernel(const BLParams prm) {
     using S = BSmp<T>;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    int pi = 0;
     const int b = blockIdx.x;
-#pragma unroll 1
-    for (int i = 1; i < prm.nplanes; ++i)
-        if (b >= prm.p[i].block0) pi = i;
-    const BLPlane pl = prm.p[pi];
+    const BLPlane pl = prm.p[vszip_find_plane(prm, b)];
     const int lb = b - pl.block0;
     const int x0 = (lb % pl.nbx) * kBX, y0 = (lb / pl.nbx) * kTileH;
     const int r = pl.radius;
@@ -845,12 +839,8 @@ __global__ __launch_bounds__(512) void bilateral_walk36_kernel(const BLParams pr
 template <typename T>
 __global__ __launch_bounds__(kBX *kBY) void bilateral_truncated_kernel(const BLParams prm) {
     using S = BSmp<T>;
-    int pi = 0;
     const int b = blockIdx.x;
-#pragma unroll 1
-    for (int i = 1; i < prm.nplanes; ++i)
-        if (b >= prm.p[i].block0) pi = i;
-    const BLPlane pl = prm.p[pi];
+    const BLPlane pl = prm.p[vszip_find_plane(prm, b)];
     const int lb = b - pl.block0;
     const int x = (lb % pl.nbx) * kBX + (int)threadIdx.x;
     const int y = (lb / pl.nbx) * kBY + (int)threadIdx.y;
@@ -1610,14 +1600,14 @@ static int bilateral_alg2(vszip_ctx *ctx, int dtype, const vszip_plane *planes, 
         // plane of the group brings a separate ref clip
         bool tiled = !ctx->opt.bilateral_untiled, joint = false;
         int max_radius = 0;
-        for (int i = done; i < nplanes && i < done + kMaxPlanesBL; ++i) {
+        for (int i = done; i < nplanes && i < done + kPlanesPerLaunch; ++i) {
             if (!cfgs[i] || (cfgs[i]->process && cfgs[i]->algorithm == 1)) break;
             tiled = tiled && cfgs[i]->radius <= kTileMaxR;
             joint = joint || (planes[i].ref && planes[i].ref != planes[i].src);
             max_radius = std::max(max_radius, cfgs[i]->radius);
         }
         const int rows_per_block = tiled ? kTileH : kBY;
-        for (; done + n < nplanes && n < kMaxPlanesBL; ++n) {
+        for (; done + n < nplanes && n < kPlanesPerLaunch; ++n) {
             const vszip_plane &s = planes[done + n];
             const vszip_bilateral_cfg *c = cfgs[done + n];
             if (c && c->process && c->algorithm == 1) break;  // next group

@@ -42,7 +42,7 @@
 #include <cstdlib>
 #include <utility>
 
-#include "common.hpp"
+#include "plane_table.hpp"
 
 namespace {
 
@@ -247,12 +247,8 @@ __global__ __launch_bounds__(64) void boxblur_ct_int_kernel(const BBParams prm) 
     __shared__ __attribute__((aligned(16))) uint32_t P[64 * PX];
 
     // block -> (plane, column tile, row band)
-    int pi = 0;
     const int b = blockIdx.x;
-#pragma unroll 1
-    for (int i = 1; i < prm.nplanes; ++i)
-        if (b >= prm.p[i].block0) pi = i;
-    const BBPlane pl = prm.p[pi];
+    const BBPlane pl = prm.p[vszip_find_plane(prm, b)];
     const int lb = b - pl.block0;
     const int tx = lb % pl.ntx;
     const int by = lb / pl.ntx;

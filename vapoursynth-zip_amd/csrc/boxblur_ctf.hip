@@ -14,11 +14,9 @@
 #include <utility>
 #include <vector>
 
-#include "common.hpp"
+#include "plane_table.hpp"
 
 namespace {
-
-constexpr int kMaxPlanesF = 192;  // planes per launch (round 4: 48 made a 64-frame 1080p call four launches, each planned as if it were the only one)
 
 struct FPlane {
     const void *src;
@@ -27,10 +25,7 @@ struct FPlane {
     int rx0, ry0, rx1, ry1;  // the rectangle of the plane this entry tiles (the whole plane, or one border strip beside the ring kernel's interior)
     int block0, nbx;
 };
-struct FParams {
-    FPlane p[kMaxPlanesF];
-    int nplanes;
-};
+typedef PlaneTable<FPlane> FParams;
 
 // boxblur_comptime.zig:50-70 — index of tap k for output index i (rows and columns alike)
 __device__ __forceinline__ int ct_tap(int k, int i, int radius, int n) {
@@ -47,17 +42,7 @@ __global__ __launch_bounds__(256) void boxblur_ct_float_kernel(const FParams prm
     __shared__ float tile[IH][IW + 1];
     __shared__ float vt[FTH][IW + 1];
     const int b = blockIdx.x;
-    int pi = 0;  // the last plane whose first block is not beyond b
-    for (int lo = 1, hi = prm.nplanes - 1; lo <= hi;) {
-        const int mid = (lo + hi) >> 1;
-        if (b >= prm.p[mid].block0) {
-            pi = mid;
-            lo = mid + 1;
-        } else {
-            hi = mid - 1;
-        }
-    }
-    const FPlane pl = prm.p[pi];
+    const FPlane pl = prm.p[vszip_find_plane(prm, b)];
     const int lb = b - pl.block0;
     const int w = pl.w, h = pl.h;
     const int x0 = pl.rx0 + (lb % pl.nbx) * FTW, y0 = pl.ry0 + (lb / pl.nbx) * FTH;
@@ -243,7 +228,7 @@ struct FRPlane {
     int block0;
 };
 struct FRParams {
-    FRPlane p[kMaxPlanesF];
+    FRPlane p[kPlanesPerLaunch];
     int nplanes, nblocks;
 };
 
@@ -457,6 +442,7 @@ __global__ __launch_bounds__(64) void boxblur_ctf_ring_kernel(const FRParams prm
     const int chunk = (prm.nblocks + 7) >> 3;  // XCD-aware: blocks b and b+8 share an XCD
     const int b = (int)(blockIdx.x & 7) * chunk + (int)(blockIdx.x >> 3);
     if (b >= prm.nblocks) return;
+    // (not vszip_find_plane: the shared search changes this kernel's register allocation — profiles/plane_table_codegen.md)
     int pi = 0;  // the last plane whose first block is not beyond b
 #pragma unroll 1
     for (int lo = 1, hi = prm.nplanes - 1; lo <= hi;) {
@@ -590,7 +576,7 @@ int run_ct_float(vszip_ctx *ctx, const vszip_plane *planes, int nplanes, int rad
     int K = 0, NR = 0, HL = 0, TWO = 0;
     RingDispatch<T, kFRMaxR>::geom(radius, K, NR, HL, TWO);
     vszip_probe_scope probe(ctx);
-    // 1. interiors: one ring launch per kMaxPlanesF planes
+    // 1. interiors: one ring launch per kPlanesPerLaunch planes
     // bands per plane: the call's waves must fit ONE resident round (r = 13: 2 waves per SIMD = 2048; one wave
     // more starts a second round and the launch takes twice as long). Greedy: the planes with
     // the most rows per band get one more band each while the round has room; a band is at least one ring period
@@ -599,11 +585,11 @@ int run_ct_float(vszip_ctx *ctx, const vszip_plane *planes, int nplanes, int rad
     std::vector<int> nb(nplanes, 0), ntxs(nplanes, 0), xbs(nplanes, 0);
     for (int i = 0; i < nplanes; ++i)
         if (ring_interior<T>(ctx, planes[i], radius, NR, HL, TWO, ntxs[i], xbs[i])) nb[i] = 1;
-    // (planned per LAUNCH: the ring planes are taken kMaxPlanesF at a time below, and each launch is a resident round of its own)
+    // (planned per LAUNCH: the ring planes are taken kPlanesPerLaunch at a time below, and each launch is a resident round of its own)
     for (int g0 = 0; g0 < nplanes;) {
         int g1 = g0, cnt = 0;
         long waves = 0;
-        for (; g1 < nplanes && cnt < kMaxPlanesF; ++g1)
+        for (; g1 < nplanes && cnt < kPlanesPerLaunch; ++g1)
             if (nb[g1]) {
                 ++cnt;
                 waves += ntxs[g1];
@@ -639,7 +625,7 @@ int run_ct_float(vszip_ctx *ctx, const vszip_plane *planes, int nplanes, int rad
     for (int done = 0; done < nplanes;) {
         FRParams prm;
         int n = 0, blocks = 0;
-        for (; done < nplanes && n < kMaxPlanesF; ++done) {
+        for (; done < nplanes && n < kPlanesPerLaunch; ++done) {
             const vszip_plane &s = planes[done];
             if (!nb[done]) continue;
             FRPlane &d = prm.p[n++];
@@ -676,7 +662,7 @@ int run_ct_float(vszip_ctx *ctx, const vszip_plane *planes, int nplanes, int rad
     };
     auto add_rect = [&](const vszip_plane &s, int rx0, int ry0, int rx1, int ry1) {
         if (rx1 <= rx0 || ry1 <= ry0) return;
-        if (n == kMaxPlanesF) flush();
+        if (n == kPlanesPerLaunch) flush();
         FPlane &d = prm.p[n++];
         d.src = s.src;
         d.dst = s.dst;

@@ -13,14 +13,12 @@
 #include <cstdlib>
 #include <vector>
 
-#include "common.hpp"
+#include "plane_table.hpp"
 
 // boxblur.hip: one integer row pass of r <= 22 through the ring kernel (VSZIP_ERR_UNSUPPORTED: not for these planes)
 int vszip_bb_ct_row_pass(vszip_ctx *ctx, int dtype, int r, const vszip_plane *planes, int nplanes);
 
 namespace {
-
-constexpr int kMaxPlanesRT = 192;  // planes per launch (round 4: 64 YUV frames are one launch per pass; 48 before)
 
 struct RPlane {
     const void *src;
@@ -29,24 +27,22 @@ struct RPlane {
     int block0;
     int aux;  // banded integer chain: this plane's first entry in the E_0 table (u32 units)
 };
-struct RParams {
-    RPlane p[kMaxPlanesRT];
-    int nplanes;
+struct RParams : PlaneTable<RPlane> {
     int radius;
     int keep;  // the output is the next pass's input: plain stores (it stays in L2 / the Infinity Cache); 0: streamed out with the nt hint
 };
 
-template <typename P>
-__device__ __forceinline__ int rt_find(const P &prm, int b) {  // block0 ascends: eight scalar steps for 192 planes (a row-per-workgroup kernel pays this per row)
-    int lo = 0, hi = prm.nplanes - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (b >= prm.p[mid].block0)
-            lo = mid;
-        else
-            hi = mid - 1;
-    }
-    return lo;
+// the launch-wide fields of a pass's tables
+inline RParams rt_table(int radius, bool keep) {
+    RParams prm;
+    prm.radius = radius;
+    prm.keep = keep ? 1 : 0;
+    return prm;
+}
+// src, dst and both pitches (in bytes) are multiples of mask + 1
+template <typename T>
+bool rt_aligned(const RPlane &q, size_t mask = 15) {
+    return ((reinterpret_cast<uintptr_t>(q.src) | reinterpret_cast<uintptr_t>(q.dst) | (uintptr_t)((size_t)q.sstride * sizeof(T)) | (uintptr_t)((size_t)q.dstride * sizeof(T))) & mask) == 0;
 }
 
 template <typename T>
@@ -68,7 +64,7 @@ __global__ __launch_bounds__(256) void boxblur_rt_hint_kernel(const RParams prm)
     extern __shared__ __attribute__((aligned(16))) uint32_t P[];
     __shared__ uint32_t wsum[4];
     const int b = blockIdx.x;
-    const RPlane pl = prm.p[rt_find(prm, b)];
+    const RPlane pl = prm.p[vszip_find_plane(prm, b)];
     const int y = b - pl.block0;
     const int w = pl.w, R = prm.radius;
     const T *s = static_cast<const T *>(pl.src) + (size_t)y * pl.sstride;
@@ -108,7 +104,7 @@ __global__ __launch_bounds__(256) void boxblur_rt_hint_kernel(const RParams prm)
 template <typename T>
 __global__ __launch_bounds__(64) void boxblur_rt_vint_kernel(const RParams prm) {
     const int b = blockIdx.x;
-    const RPlane pl = prm.p[rt_find(prm, b)];
+    const RPlane pl = prm.p[vszip_find_plane(prm, b)];
     const int x = (b - pl.block0) * 64 + threadIdx.x;
     if (x >= pl.w) return;
     const int len = pl.h, R = prm.radius;
@@ -211,10 +207,9 @@ struct RtVec {
     }
 };
 
-struct RVParams {
-    RPlane p[kMaxPlanesRT];
-    int ncg[kMaxPlanesRT];  // column groups (64 lanes x V columns) per plane
-    int nplanes, radius, band;
+struct RVParams : PlaneTable<RPlane> {
+    int ncg[capacity];  // column groups (64 lanes x V columns) per plane
+    int radius, band;
     int keep;
 };
 
@@ -235,7 +230,7 @@ __global__ __launch_bounds__(64) void boxblur_rt_vband_kernel(const RVParams prm
     const int D = 2 * prm.radius + 2;
     auto slot = [&](int row) -> uint4 & { return vring[(row % D) * 64 + (int)threadIdx.x]; };
     const int b = blockIdx.x;
-    const int pi = rt_find(prm, b);
+    const int pi = vszip_find_plane(prm, b);
     const RPlane pl = prm.p[pi];
     const int lb = b - pl.block0, ncg = prm.ncg[pi];
     const int x0 = ((lb % ncg) * 64 + (int)threadIdx.x) * V;
@@ -355,7 +350,7 @@ __global__ __launch_bounds__(64) void boxblur_rt_hrow_kernel(const RParams prm) 
     constexpr int V = X::V, CH = 64 * V;
     extern __shared__ __attribute__((aligned(16))) uint32_t P[];
     const int b = blockIdx.x;
-    const RPlane pl = prm.p[rt_find(prm, b)];
+    const RPlane pl = prm.p[vszip_find_plane(prm, b)];
     const int y = b - pl.block0;
     const int w = pl.w, R = prm.radius;
     const T *s = static_cast<const T *>(pl.src) + (size_t)y * pl.sstride;
@@ -443,7 +438,7 @@ __global__ __launch_bounds__(64) void boxblur_rt_hring_kernel(const RParams prm)
     static_assert((1 << LV) == V && (1 << LCH) == CH, "chunk geometry");
     __shared__ __attribute__((aligned(16))) uint32_t P[kRing];
     const int b = blockIdx.x;
-    const RPlane pl = prm.p[rt_find(prm, b)];
+    const RPlane pl = prm.p[vszip_find_plane(prm, b)];
     const int y = b - pl.block0;
     const int w = pl.w, R = prm.radius;
     const T *s = static_cast<const T *>(pl.src) + (size_t)y * pl.sstride;
@@ -593,7 +588,7 @@ __device__ __forceinline__ int rtf_out(int x, int R) { return x <= R ? R - x : x
 template <typename T>
 __global__ __launch_bounds__(64) void boxblur_rt_float_v_kernel(const RParams prm) {
     const int b = blockIdx.x;
-    const RPlane pl = prm.p[rt_find(prm, b)];
+    const RPlane pl = prm.p[vszip_find_plane(prm, b)];
     // kLW columns per wave. Measured on 8 4K YUV420PS frames, 3+3 passes of r = 5 (k fps): 64 -> 5.9, 32 -> 5.2,
     // 16 -> 3.6; a variant with 16-byte loads (4 columns per lane, a quarter of the waves) 5.6: the pass is bound by
     // the number of row requests in flight, not by a wave's chain.
@@ -665,7 +660,7 @@ __global__ __launch_bounds__(64) void boxblur_rt_float_h_kernel(const RParams pr
     constexpr int RB = VSZIP_RTF_RB;
     __shared__ float tin[RB][65], tout[RB][65];
     const int b = blockIdx.x;
-    const RPlane pl = prm.p[rt_find(prm, b)];
+    const RPlane pl = prm.p[vszip_find_plane(prm, b)];
     const int lane = threadIdx.x;
     const int y0 = (b - pl.block0) * RB;
     const int rows = min(RB, pl.h - y0), len = pl.w, R = prm.radius;
@@ -932,7 +927,7 @@ __global__ __launch_bounds__(64) void boxblur_rt_float_vchain_kernel(const RPara
     typedef T Raw __attribute__((ext_vector_type(4)));
     typedef E f32x4 __attribute__((ext_vector_type(4)));  // (four LDS samples)
     const int b = blockIdx.x, lane = threadIdx.x;
-    const RPlane pl = prm.p[rt_find(prm, b)];
+    const RPlane pl = prm.p[vszip_find_plane(prm, b)];
     const int i0 = (b - pl.block0) * 64, i = i0 + lane;
     const bool ok = i < pl.w;
     const int qrow = lane >> 4, qcol = 4 * (lane & 15);
@@ -1071,7 +1066,7 @@ __global__ __launch_bounds__(64) void boxblur_rt_ichain_kernel(const RParams prm
     typedef T Raw __attribute__((ext_vector_type(4)));
     typedef E e4 __attribute__((ext_vector_type(4)));
     const int b = blockIdx.x, lane = threadIdx.x;
-    const RPlane pl = prm.p[rt_find(prm, b)];
+    const RPlane pl = prm.p[vszip_find_plane(prm, b)];
     const int ncg = (pl.w + 63) / 64;
     const int lb = b - pl.block0;
     const int cg = MODE == 2 ? lb % ncg : lb, band = MODE == 2 ? lb / ncg : 0;
@@ -1230,7 +1225,7 @@ __global__ __launch_bounds__(64) void boxblur_rt_float_hchain_kernel(const RPara
     extern __shared__ float fc_lds[];  // [D][P][RB] rings
     __shared__ float tin[RB][65], tout[RB][65];
     const int b = blockIdx.x, lane = threadIdx.x;
-    const RPlane pl = prm.p[rt_find(prm, b)];
+    const RPlane pl = prm.p[vszip_find_plane(prm, b)];
     const int y0 = (b - pl.block0) * RB;
     const int rows = min(RB, pl.h - y0), len = pl.w;
     const T *s = static_cast<const T *>(pl.src) + (size_t)y0 * pl.sstride;
@@ -1375,7 +1370,7 @@ __global__ __launch_bounds__(kHmNT) void boxblur_rt_hmulti_kernel(const RParams 
     __shared__ uint32_t P[2][16 * kHmCols];
     __shared__ uint32_t wtot[2][4];
     const int b = blockIdx.x;
-    const RPlane pl = prm.p[rt_find(prm, b)];
+    const RPlane pl = prm.p[vszip_find_plane(prm, b)];
     const int y = b - pl.block0;
     const int w = pl.w, R = prm.radius;
     const T *s = static_cast<const T *>(pl.src) + (size_t)y * pl.sstride;
@@ -1467,7 +1462,7 @@ template <typename T, int R>
 __global__ __launch_bounds__(64) void boxblur_rt_hsmall_kernel(const RParams prm, const int npass, const int pitch /* u16 elements per LDS buffer */) {
     extern __shared__ __attribute__((aligned(16))) uint16_t hs[];
     const int b = blockIdx.x;
-    const RPlane pl = prm.p[rt_find(prm, b)];
+    const RPlane pl = prm.p[vszip_find_plane(prm, b)];
     const int y = b - pl.block0, w = pl.w, lane = (int)threadIdx.x;
     const T *s = static_cast<const T *>(pl.src) + (size_t)y * pl.sstride;
     T *d = static_cast<T *>(pl.dst) + (size_t)y * pl.dstride;
@@ -1673,10 +1668,8 @@ __device__ __forceinline__ void vs_feed(VsCtx<T, P> &c, const uint32_t (&x)[8], 
 template <typename T, int P>
 __global__ __launch_bounds__(64) void boxblur_rt_vsmall_kernel(const RVParams prm) {
     extern __shared__ __attribute__((aligned(16))) uint4 vsr[];  // [stage][slot][lane]
-    int pi = 0;
     const int b = blockIdx.x;
-    for (int i = 1; i < prm.nplanes; ++i)
-        if (b >= prm.p[i].block0) pi = i;
+    const int pi = vszip_find_plane(prm, b);
     const RPlane pl = prm.p[pi];
     const int lb = b - pl.block0, ncg = prm.ncg[pi], lane = (int)threadIdx.x;
     const int x0 = ((lb % ncg) * 64 + lane) * 8;
@@ -1769,7 +1762,7 @@ template <typename T>
 __global__ __launch_bounds__(256) void rt_transpose_kernel(const RParams prm) {
     __shared__ T tile[64][64 + 2];
     const int b = blockIdx.x;
-    const RPlane pl = prm.p[rt_find(prm, b)];
+    const RPlane pl = prm.p[vszip_find_plane(prm, b)];
     const int lb = b - pl.block0;
     const int nbx = (pl.w + 63) / 64;
     const int bx = (lb % nbx) * 64, by = (lb / nbx) * 64;
@@ -1789,40 +1782,33 @@ template <typename T>
 bool hsmall_ok(const vszip_ctx *ctx, const std::vector<RPlane> &pl, int radius, int npass) {
     if (!std::is_integral<T>::value || sizeof(T) > 2 || npass < 2 || radius < 1 || radius > kHsMaxR || ctx->opt.rt_no_hsmall) return false;
     for (const RPlane &q : pl) {
-        const uintptr_t bits = reinterpret_cast<uintptr_t>(q.src) | reinterpret_cast<uintptr_t>(q.dst) | (uintptr_t)((size_t)q.sstride * sizeof(T)) | (uintptr_t)((size_t)q.dstride * sizeof(T));
-        if ((bits & 15) != 0 || q.w <= 2 * radius || q.w > kHsMaxW || q.sstride < ((q.w + 7) / 8) * 8 || q.dstride < ((q.w + 7) / 8) * 8) return false;
+        if (!rt_aligned<T>(q) || q.w <= 2 * radius || q.w > kHsMaxW || q.sstride < ((q.w + 7) / 8) * 8 || q.dstride < ((q.w + 7) / 8) * 8) return false;
     }
     return true;
 }
 template <typename T>
 int launch_hsmall(vszip_ctx *ctx, const std::vector<RPlane> &pl, int radius, int npass, bool keep) {
-    size_t done = 0;
-    while (done < pl.size()) {
-        RParams prm;
-        const int n = (int)std::min<size_t>(kMaxPlanesRT, pl.size() - done);
-        prm.nplanes = n;
-        prm.radius = radius;
-        prm.keep = keep ? 1 : 0;
-        int blocks = 0, maxw = 0;
-        for (int i = 0; i < n; ++i) {
-            prm.p[i] = pl[done + i];
-            prm.p[i].block0 = blocks;
-            blocks += prm.p[i].h;
-            maxw = std::max(maxw, prm.p[i].w);
-        }
-        const int pitch = ((maxw + 7) / 8) * 8 + 2 * kHsHalo + 16;  // halo room on the left, the row in whole groups, halo room on the right, slack for the last group's reads
-        const size_t lds = (size_t)2 * pitch * sizeof(uint16_t);
+    RParams prm = rt_table(radius, keep);
+    return vszip_for_each_table(
+        ctx, prm, (int)pl.size(),
+        [&](RPlane &d, int i) -> int {
+            d = pl[i];
+            return d.h;
+        },
+        [&](const RParams &prm, int blocks, int) -> int {
+            int maxw = 0;
+            for (int i = 0; i < prm.nplanes; ++i) maxw = std::max(maxw, prm.p[i].w);
+            const int pitch = ((maxw + 7) / 8) * 8 + 2 * kHsHalo + 16;  // halo room on the left, the row in whole groups, halo room on the right, slack for the last group's reads
+            const size_t lds = (size_t)2 * pitch * sizeof(uint16_t);
 #define VSZIP_HS(RR) case RR: hipLaunchKernelGGL((boxblur_rt_hsmall_kernel<T, RR>), dim3(blocks), dim3(64), lds, ctx->stream, prm, npass, pitch); break
-        switch (radius) {
-            VSZIP_HS(1); VSZIP_HS(2); VSZIP_HS(3); VSZIP_HS(4); VSZIP_HS(5); VSZIP_HS(6); VSZIP_HS(7); VSZIP_HS(8);
-            VSZIP_HS(9); VSZIP_HS(10); VSZIP_HS(11); VSZIP_HS(12); VSZIP_HS(13); VSZIP_HS(14); VSZIP_HS(15);
-            default: hipLaunchKernelGGL((boxblur_rt_hsmall_kernel<T, 16>), dim3(blocks), dim3(64), lds, ctx->stream, prm, npass, pitch); break;
-        }
+            switch (radius) {
+                VSZIP_HS(1); VSZIP_HS(2); VSZIP_HS(3); VSZIP_HS(4); VSZIP_HS(5); VSZIP_HS(6); VSZIP_HS(7); VSZIP_HS(8);
+                VSZIP_HS(9); VSZIP_HS(10); VSZIP_HS(11); VSZIP_HS(12); VSZIP_HS(13); VSZIP_HS(14); VSZIP_HS(15);
+                default: hipLaunchKernelGGL((boxblur_rt_hsmall_kernel<T, 16>), dim3(blocks), dim3(64), lds, ctx->stream, prm, npass, pitch); break;
+            }
 #undef VSZIP_HS
-        VSZIP_HIP_CHECK(ctx, hipGetLastError());
-        done += n;
-    }
-    return VSZIP_OK;
+            return VSZIP_OK;
+        });
 }
 
 #ifdef VSZIP_DEV_VARIANTS  // measured slower than what the default build runs (options.inc)
@@ -1840,17 +1826,17 @@ bool vsmall_ok(const vszip_ctx *ctx, const std::vector<RPlane> &pl, int radius, 
     if (!std::is_integral<T>::value || sizeof(T) > 2 || npass < 2 || npass > max_pass || radius < 1 || radius > kVsMaxR || ctx->opt.rt_no_vsmall) return false;
     if ((size_t)npass * (2 * radius + 2) * 1024 > 40 * 1024) return false;  // the rings: four waves a CU at least
     for (const RPlane &q : pl) {
-        const uintptr_t bits = reinterpret_cast<uintptr_t>(q.src) | reinterpret_cast<uintptr_t>(q.dst) | (uintptr_t)((size_t)q.sstride * sizeof(T)) | (uintptr_t)((size_t)q.dstride * sizeof(T));
-        if ((bits & 15) != 0 || q.h <= 2 * npass * radius + 2 || q.sstride < ((q.w + 7) / 8) * 8 || q.dstride < ((q.w + 7) / 8) * 8) return false;
+        if (!rt_aligned<T>(q) || q.h <= 2 * npass * radius + 2 || q.sstride < ((q.w + 7) / 8) * 8 || q.dstride < ((q.w + 7) / 8) * 8) return false;
     }
     return true;
 }
 template <typename T>
 int launch_vsmall(vszip_ctx *ctx, const std::vector<RPlane> &pl, int radius, int npass, bool keep) {
+    // (not vszip_for_each_table: a plane's block count depends on the band length, which is chosen from the whole table)
     size_t done = 0;
     while (done < pl.size()) {
         RVParams vp;
-        const int n = (int)std::min<size_t>(kMaxPlanesRT, pl.size() - done);
+        const int n = (int)std::min<size_t>(RVParams::capacity, pl.size() - done);
         vp.nplanes = n;
         vp.radius = radius;
         vp.keep = keep ? 1 : 0;
@@ -1911,94 +1897,84 @@ int launch_pass(vszip_ctx *ctx, const std::vector<RPlane> &pl, int radius, bool 
             if (rc != VSZIP_ERR_UNSUPPORTED) return rc;
         }
     }
-    size_t done = 0;
-    while (done < pl.size()) {
-        RParams prm;
-        const int n = (int)std::min<size_t>(kMaxPlanesRT, pl.size() - done);
-        prm.nplanes = n;
-        prm.radius = radius;
-        prm.keep = keep ? 1 : 0;
-        int blocks = 0, maxw = 0;
-        for (int i = 0; i < n; ++i) {
-            prm.p[i] = pl[done + i];
-            prm.p[i].block0 = blocks;
-            if (is_int && !vertical)
-                blocks += prm.p[i].h;
-            else if (!is_int && !vertical)
-                blocks += (prm.p[i].h + VSZIP_RTF_RB - 1) / VSZIP_RTF_RB;
-            else if (!is_int)
-                blocks += (prm.p[i].w + VSZIP_RTF_LW - 1) / VSZIP_RTF_LW;
-            else
-                blocks += ((vertical ? prm.p[i].w : prm.p[i].h) + 63) / 64;
-            maxw = std::max(maxw, prm.p[i].w);
-        }
-        if constexpr (is_int) {
-            bool aligned = true;
-            for (int i = 0; i < n; ++i) {
-                const RPlane &q = prm.p[i];
-                aligned = aligned && (((reinterpret_cast<uintptr_t>(q.src) | reinterpret_cast<uintptr_t>(q.dst) | (uintptr_t)((size_t)q.sstride * sizeof(T)) |
-                                        (uintptr_t)((size_t)q.dstride * sizeof(T))) & 15) == 0) && q.sstride >= ((q.w + RtVec<T>::V - 1) / RtVec<T>::V) * RtVec<T>::V;
-            }
-            if (aligned && !vertical) {
-                constexpr int CH = 64 * RtVec<T>::V;
-                if (radius < CH - 1 && !ctx->opt.rt_hrow) {
-                    // virtual (mirror-extended) rows when every row is whole lane groups and wider than its halos
-                    bool virt = !ctx->opt.rt_no_virt;
-                    for (int i = 0; i < n; ++i) virt = virt && prm.p[i].w % RtVec<T>::V == 0 && prm.p[i].w >= radius + 1 + RtVec<T>::V;
-                    if (virt)
-                        hipLaunchKernelGGL((boxblur_rt_hring_kernel<T, true>), dim3(blocks), dim3(64), 0, ctx->stream, prm);
+    RParams prm = rt_table(radius, keep);
+    return vszip_for_each_table(
+        ctx, prm, (int)pl.size(),
+        [&](RPlane &d, int i) -> int {
+            d = pl[i];
+            if (is_int && !vertical) return d.h;
+            if (!is_int && !vertical) return (d.h + VSZIP_RTF_RB - 1) / VSZIP_RTF_RB;
+            if (!is_int) return (d.w + VSZIP_RTF_LW - 1) / VSZIP_RTF_LW;
+            return ((vertical ? d.w : d.h) + 63) / 64;
+        },
+        [&](const RParams &prm, int blocks, int) -> int {
+            const int n = prm.nplanes;
+            int maxw = 0;
+            for (int i = 0; i < n; ++i) maxw = std::max(maxw, prm.p[i].w);
+            if constexpr (is_int) {
+                bool aligned = true;
+                for (int i = 0; i < n; ++i) {
+                    const RPlane &q = prm.p[i];
+                    aligned = aligned && rt_aligned<T>(q) && q.sstride >= ((q.w + RtVec<T>::V - 1) / RtVec<T>::V) * RtVec<T>::V;
+                }
+                if (aligned && !vertical) {
+                    constexpr int CH = 64 * RtVec<T>::V;
+                    if (radius < CH - 1 && !ctx->opt.rt_hrow) {
+                        // virtual (mirror-extended) rows when every row is whole lane groups and wider than its halos
+                        bool virt = !ctx->opt.rt_no_virt;
+                        for (int i = 0; i < n; ++i) virt = virt && prm.p[i].w % RtVec<T>::V == 0 && prm.p[i].w >= radius + 1 + RtVec<T>::V;
+                        if (virt)
+                            hipLaunchKernelGGL((boxblur_rt_hring_kernel<T, true>), dim3(blocks), dim3(64), 0, ctx->stream, prm);
+                        else
+                            hipLaunchKernelGGL((boxblur_rt_hring_kernel<T, false>), dim3(blocks), dim3(64), 0, ctx->stream, prm);
+                    } else {
+                        const size_t lds = (size_t)((maxw + CH - 1) / CH) * CH * sizeof(uint32_t);
+                        if (lds > 64000)  // only the whole-row-prefix kernels keep a row in LDS; the ring kernel above serves any width
+                            return vszip_set_error(ctx, VSZIP_ERR_UNSUPPORTED, "BoxBlur: a horizontal radius of %d on rows longer than 15000 samples is not built", radius);
+                        hipLaunchKernelGGL((boxblur_rt_hrow_kernel<T>), dim3(blocks), dim3(64), lds, ctx->stream, prm);
+                    }
+                } else if (aligned) {
+                    RVParams vp;
+                    vp.nplanes = n;
+                    vp.radius = radius;
+                    vp.keep = prm.keep;
+                    // bands: enough waves to fill the chip, long enough that the 3r+2 warm-up rows stay a fraction
+                    long colgroups = 0;
+                    int maxh = 0;
+                    for (int i = 0; i < n; ++i) {
+                        colgroups += (prm.p[i].w + 64 * RtVec<T>::V - 1) / (64 * RtVec<T>::V);
+                        maxh = std::max(maxh, prm.p[i].h);
+                    }
+                    int band = std::max(64, 4 * radius);
+                    while (band < maxh && colgroups * ((maxh + band - 1) / band) > 16384) band *= 2;
+                    if (ctx->opt.rt_vband > 0) band = std::max(8, (int)ctx->opt.rt_vband);  // development sweep knob (-DVSZIP_DEV_VARIANTS)
+                    vp.band = band;
+                    int vb = 0;
+                    for (int i = 0; i < n; ++i) {
+                        vp.p[i] = prm.p[i];
+                        vp.p[i].block0 = vb;
+                        vp.ncg[i] = (prm.p[i].w + 64 * RtVec<T>::V - 1) / (64 * RtVec<T>::V);
+                        vb += vp.ncg[i] * ((prm.p[i].h + band - 1) / band);
+                    }
+                    if (radius <= (ctx->opt.rt_vring_maxr > 0 ? (int)ctx->opt.rt_vring_maxr : kVRingMaxR) && !ctx->opt.rt_no_vring)
+                        hipLaunchKernelGGL((boxblur_rt_vband_kernel<T, true>), dim3(vb), dim3(64), (size_t)(2 * radius + 2) * 64 * sizeof(uint4), ctx->stream, vp);
                     else
-                        hipLaunchKernelGGL((boxblur_rt_hring_kernel<T, false>), dim3(blocks), dim3(64), 0, ctx->stream, prm);
+                        hipLaunchKernelGGL((boxblur_rt_vband_kernel<T, false>), dim3(vb), dim3(64), 0, ctx->stream, vp);
+                } else if (!vertical) {
+                    if ((size_t)maxw * sizeof(uint32_t) > 64000)
+                        return vszip_set_error(ctx, VSZIP_ERR_UNSUPPORTED, "BoxBlur: rows longer than 16000 samples need 16-byte aligned planes on the RT integer path");
+                    hipLaunchKernelGGL((boxblur_rt_hint_kernel<T>), dim3(blocks), dim3(256), (size_t)maxw * sizeof(uint32_t), ctx->stream, prm);
                 } else {
-                    const size_t lds = (size_t)((maxw + CH - 1) / CH) * CH * sizeof(uint32_t);
-                    if (lds > 64000)  // only the whole-row-prefix kernels keep a row in LDS; the ring kernel above serves any width
-                        return vszip_set_error(ctx, VSZIP_ERR_UNSUPPORTED, "BoxBlur: a horizontal radius of %d on rows longer than 15000 samples is not built", radius);
-                    hipLaunchKernelGGL((boxblur_rt_hrow_kernel<T>), dim3(blocks), dim3(64), lds, ctx->stream, prm);
+                    hipLaunchKernelGGL((boxblur_rt_vint_kernel<T>), dim3(blocks), dim3(64), 0, ctx->stream, prm);
                 }
-            } else if (aligned) {
-                RVParams vp;
-                vp.nplanes = n;
-                vp.radius = radius;
-                vp.keep = keep ? 1 : 0;
-                // bands: enough waves to fill the chip, long enough that the 3r+2 warm-up rows stay a fraction
-                long colgroups = 0;
-                int maxh = 0;
-                for (int i = 0; i < n; ++i) {
-                    colgroups += (prm.p[i].w + 64 * RtVec<T>::V - 1) / (64 * RtVec<T>::V);
-                    maxh = std::max(maxh, prm.p[i].h);
-                }
-                int band = std::max(64, 4 * radius);
-                while (band < maxh && colgroups * ((maxh + band - 1) / band) > 16384) band *= 2;
-                if (ctx->opt.rt_vband > 0) band = std::max(8, (int)ctx->opt.rt_vband);  // development sweep knob (-DVSZIP_DEV_VARIANTS)
-                vp.band = band;
-                int vb = 0;
-                for (int i = 0; i < n; ++i) {
-                    vp.p[i] = prm.p[i];
-                    vp.p[i].block0 = vb;
-                    vp.ncg[i] = (prm.p[i].w + 64 * RtVec<T>::V - 1) / (64 * RtVec<T>::V);
-                    vb += vp.ncg[i] * ((prm.p[i].h + band - 1) / band);
-                }
-                if (radius <= (ctx->opt.rt_vring_maxr > 0 ? (int)ctx->opt.rt_vring_maxr : kVRingMaxR) && !ctx->opt.rt_no_vring)
-                    hipLaunchKernelGGL((boxblur_rt_vband_kernel<T, true>), dim3(vb), dim3(64), (size_t)(2 * radius + 2) * 64 * sizeof(uint4), ctx->stream, vp);
-                else
-                    hipLaunchKernelGGL((boxblur_rt_vband_kernel<T, false>), dim3(vb), dim3(64), 0, ctx->stream, vp);
-            } else if (!vertical) {
-                if ((size_t)maxw * sizeof(uint32_t) > 64000)
-                    return vszip_set_error(ctx, VSZIP_ERR_UNSUPPORTED, "BoxBlur: rows longer than 16000 samples need 16-byte aligned planes on the RT integer path");
-                hipLaunchKernelGGL((boxblur_rt_hint_kernel<T>), dim3(blocks), dim3(256), (size_t)maxw * sizeof(uint32_t), ctx->stream, prm);
             } else {
-                hipLaunchKernelGGL((boxblur_rt_vint_kernel<T>), dim3(blocks), dim3(64), 0, ctx->stream, prm);
+                if (vertical)
+                    hipLaunchKernelGGL((boxblur_rt_float_v_kernel<T>), dim3(blocks), dim3(64), 0, ctx->stream, prm);
+                else
+                    hipLaunchKernelGGL((boxblur_rt_float_h_kernel<T>), dim3(blocks), dim3(64), 0, ctx->stream, prm);
             }
-        } else {
-            if (vertical)
-                hipLaunchKernelGGL((boxblur_rt_float_v_kernel<T>), dim3(blocks), dim3(64), 0, ctx->stream, prm);
-            else
-                hipLaunchKernelGGL((boxblur_rt_float_h_kernel<T>), dim3(blocks), dim3(64), 0, ctx->stream, prm);
-        }
-        VSZIP_HIP_CHECK(ctx, hipGetLastError());
-        done += n;
-    }
-    return VSZIP_OK;
+            return VSZIP_OK;
+        });
 }
 
 // The float chain kernels: 2 ... 5 passes, lines of at least 2 R + 2 samples, rings within one workgroup's LDS.
@@ -2033,8 +2009,7 @@ bool fchain_ok(const vszip_ctx *ctx, const std::vector<RPlane> &pl, int radius, 
     for (const RPlane &q : pl) {
         if ((vertical ? q.h : q.w) < 2 * radius + 2) return false;
         if (vertical) {  // rows go four samples a lane
-            const uintptr_t bits = reinterpret_cast<uintptr_t>(q.src) | reinterpret_cast<uintptr_t>(q.dst) | (uintptr_t)((size_t)q.sstride * sizeof(T)) | (uintptr_t)((size_t)q.dstride * sizeof(T));
-            if ((bits & (4 * sizeof(T) - 1)) != 0 || q.sstride < ((q.w + 3) & ~3) || q.w < 4) return false;
+            if (!rt_aligned<T>(q, 4 * sizeof(T) - 1) || q.sstride < ((q.w + 3) & ~3) || q.w < 4) return false;
         }
     }
     return true;
@@ -2042,21 +2017,16 @@ bool fchain_ok(const vszip_ctx *ctx, const std::vector<RPlane> &pl, int radius, 
 
 template <typename T>
 int launch_fchain(vszip_ctx *ctx, const std::vector<RPlane> &pl, int radius, int npass, bool vertical, bool keep) {
-    size_t done = 0;
-    while (done < pl.size()) {
-        RParams prm;
-        const int n = (int)std::min<size_t>(kMaxPlanesRT, pl.size() - done);
-        prm.nplanes = n;
-        prm.radius = radius;
-        prm.keep = keep ? 1 : 0;
-        int blocks = 0;
-        for (int i = 0; i < n; ++i) {
-            prm.p[i] = pl[done + i];
-            prm.p[i].block0 = blocks;
-            blocks += vertical ? (prm.p[i].w + 63) / 64 : (prm.p[i].h + kFcRB - 1) / kFcRB;
-        }
-        const int D = 2 * radius + 3;
-        const size_t lds = vertical ? ((size_t)npass * D + kFcPf + 8) * 64 * sizeof(typename FcArith<T>::E) : (size_t)npass * D * kFcRB * sizeof(float);
+    RParams prm = rt_table(radius, keep);
+    return vszip_for_each_table(
+        ctx, prm, (int)pl.size(),
+        [&](RPlane &d, int i) -> int {
+            d = pl[i];
+            return vertical ? (d.w + 63) / 64 : (d.h + kFcRB - 1) / kFcRB;
+        },
+        [&](const RParams &prm, int blocks, int) -> int {
+            const int D = 2 * radius + 3;
+            const size_t lds = vertical ? ((size_t)npass * D + kFcPf + 8) * 64 * sizeof(typename FcArith<T>::E) : (size_t)npass * D * kFcRB * sizeof(float);
 #define VSZIP_FC_LAUNCH(PP)                                                                                                        \
     case PP:                                                                                                                       \
         if (vertical) {                                                                                                            \
@@ -2066,17 +2036,15 @@ int launch_fchain(vszip_ctx *ctx, const std::vector<RPlane> &pl, int radius, int
                 hipLaunchKernelGGL((boxblur_rt_float_hchain_kernel<T, PP>), dim3(blocks), dim3(64), lds, ctx->stream, prm);       \
         }                                                                                                                          \
         break;
-        switch (npass) {
-            VSZIP_FC_LAUNCH(2)
-            VSZIP_FC_LAUNCH(3)
-            VSZIP_FC_LAUNCH(4)
-            VSZIP_FC_LAUNCH(5)
-        }
+            switch (npass) {
+                VSZIP_FC_LAUNCH(2)
+                VSZIP_FC_LAUNCH(3)
+                VSZIP_FC_LAUNCH(4)
+                VSZIP_FC_LAUNCH(5)
+            }
 #undef VSZIP_FC_LAUNCH
-        VSZIP_HIP_CHECK(ctx, hipGetLastError());
-        done += n;
-    }
-    return VSZIP_OK;
+            return VSZIP_OK;
+        });
 }
 
 // The banded integer vertical chain (boxblur_rt_ichain_kernel): the planes qualify when the unbanded chain does, are tall enough for the mirror
@@ -2151,43 +2119,40 @@ size_t ichain_table_bytes(const std::vector<RPlane> &pl) {
 template <typename T>
 int launch_ichain_banded(vszip_ctx *ctx, const std::vector<RPlane> &pl, int radius, int npass, bool keep, int band_rows, uint32_t *kk_tab) {
     if constexpr (std::is_integral<T>::value && sizeof(T) <= 2) {
-        size_t done = 0, kk_off = 0;
-        while (done < pl.size()) {
-            RParams prm, pe0;
-            const int n = (int)std::min<size_t>(kMaxPlanesRT, pl.size() - done);
-            prm.nplanes = pe0.nplanes = n;
-            prm.radius = pe0.radius = radius;
-            prm.keep = pe0.keep = keep ? 1 : 0;
-            int blocks = 0, blocks0 = 0;
-            for (int i = 0; i < n; ++i) {
-                prm.p[i] = pl[done + i];
-                const int ncg = (prm.p[i].w + 63) / 64;
-                prm.p[i].aux = (int)kk_off;
+        size_t kk_off = 0;
+        RParams prm = rt_table(radius, keep);
+        return vszip_for_each_table(
+            ctx, prm, (int)pl.size(),
+            [&](RPlane &d, int i) -> int {
+                d = pl[i];
+                const int ncg = (d.w + 63) / 64;
+                d.aux = (int)kk_off;
                 kk_off += (size_t)ncg * 64 * kFcMaxPass;
-                pe0.p[i] = prm.p[i];
-                prm.p[i].block0 = blocks;
-                pe0.p[i].block0 = blocks0;
-                blocks += ncg * ((prm.p[i].h + band_rows - 1) / band_rows);
-                blocks0 += ncg;
-            }
-            const int D = 2 * radius + 3;
-            const size_t lds = ((size_t)npass * D + kFcPf + 8) * 64 * sizeof(uint16_t);
+                return ncg * ((d.h + band_rows - 1) / band_rows);
+            },
+            [&](const RParams &prm, int blocks, int) -> int {
+                RParams pe0 = prm;  // the launch that fills the table of constants: one workgroup per column group
+                int blocks0 = 0;
+                for (int i = 0; i < pe0.nplanes; ++i) {
+                    pe0.p[i].block0 = blocks0;
+                    blocks0 += (pe0.p[i].w + 63) / 64;
+                }
+                const int D = 2 * radius + 3;
+                const size_t lds = ((size_t)npass * D + kFcPf + 8) * 64 * sizeof(uint16_t);
 #define VSZIP_IC_LAUNCH(PP)                                                                                                              \
     case PP:                                                                                                                             \
         hipLaunchKernelGGL((boxblur_rt_ichain_kernel<T, PP, 1>), dim3(blocks0), dim3(64), lds, ctx->stream, pe0, kk_tab, band_rows);     \
         hipLaunchKernelGGL((boxblur_rt_ichain_kernel<T, PP, 2>), dim3(blocks), dim3(64), lds, ctx->stream, prm, kk_tab, band_rows);      \
         break;
-            switch (npass) {
-                VSZIP_IC_LAUNCH(2)
-                VSZIP_IC_LAUNCH(3)
-                VSZIP_IC_LAUNCH(4)
-                VSZIP_IC_LAUNCH(5)
-            }
+                switch (npass) {
+                    VSZIP_IC_LAUNCH(2)
+                    VSZIP_IC_LAUNCH(3)
+                    VSZIP_IC_LAUNCH(4)
+                    VSZIP_IC_LAUNCH(5)
+                }
 #undef VSZIP_IC_LAUNCH
-            VSZIP_HIP_CHECK(ctx, hipGetLastError());
-            done += n;
-        }
-        return VSZIP_OK;
+                return VSZIP_OK;
+            });
     } else {
         return VSZIP_ERR_ARG;
     }
@@ -2241,17 +2206,10 @@ int run_rt(vszip_ctx *ctx, const vszip_plane *planes, int nplanes, int hradius, 
             int which = 0;
             // one step over all planes: kind 0 = fused passes along the rows, 1 = transpose; `to_dst`: into the caller's planes
             auto step = [&](int kind, int radius, int npass, bool to_dst) -> int {
-                size_t done = 0;
-                while (done < (size_t)nplanes) {
-                    RParams prm;
-                    const int n = (int)std::min<size_t>(kMaxPlanesRT, nplanes - done);
-                    prm.nplanes = n;
-                    prm.radius = radius;
-                    prm.keep = to_dst ? 0 : 1;
-                    int blocks = 0;
-                    for (int i = 0; i < n; ++i) {
-                        const int gi = (int)done + i;
-                        RPlane &r = prm.p[i];
+                RParams prm = rt_table(radius, !to_dst);
+                const int st = vszip_for_each_table(
+                    ctx, prm, nplanes,
+                    [&](RPlane &r, int gi) -> int {
                         r.src = cur[gi].ptr;
                         r.sstride = cur[gi].stride;
                         r.w = cur[gi].w;
@@ -2264,21 +2222,20 @@ int run_rt(vszip_ctx *ctx, const vszip_plane *planes, int nplanes, int hradius, 
                             r.dst = buf[which] + poff[gi];
                             r.dstride = (ow + 63) & ~63;
                         }
-                        r.block0 = blocks;
-                        blocks += kind == 1 ? ((r.w + 63) / 64) * ((r.h + 63) / 64) : r.h;
-                    }
-                    if (kind == 1)
-                        hipLaunchKernelGGL((rt_transpose_kernel<T>), dim3(blocks), dim3(256), 0, ctx->stream, prm);
-                    else
-                        hipLaunchKernelGGL((boxblur_rt_hmulti_kernel<T>), dim3(blocks), dim3(kHmNT), 0, ctx->stream, prm, npass);
-                    VSZIP_HIP_CHECK(ctx, hipGetLastError());
-                    for (int i = 0; i < n; ++i) {
-                        const int gi = (int)done + i;
-                        const RPlane &r = prm.p[i];
-                        cur[gi] = kind == 1 ? Cur{r.dst, r.dstride, r.h, r.w} : Cur{r.dst, r.dstride, r.w, r.h};
-                    }
-                    done += n;
-                }
+                        return kind == 1 ? ((r.w + 63) / 64) * ((r.h + 63) / 64) : r.h;
+                    },
+                    [&](const RParams &prm, int blocks, int first) -> int {
+                        if (kind == 1)
+                            hipLaunchKernelGGL((rt_transpose_kernel<T>), dim3(blocks), dim3(256), 0, ctx->stream, prm);
+                        else
+                            hipLaunchKernelGGL((boxblur_rt_hmulti_kernel<T>), dim3(blocks), dim3(kHmNT), 0, ctx->stream, prm, npass);
+                        for (int i = 0; i < prm.nplanes; ++i) {
+                            const RPlane &r = prm.p[i];
+                            cur[first + i] = kind == 1 ? Cur{r.dst, r.dstride, r.h, r.w} : Cur{r.dst, r.dstride, r.w, r.h};
+                        }
+                        return VSZIP_OK;
+                    });
+                if (st != VSZIP_OK) return st;
                 which ^= 1;
                 return VSZIP_OK;
             };

@@ -12,11 +12,10 @@
 // Bit-exact with the reference: integer counts in any order, then the reference's f32 operations in its order (-ffp-contract=off).
 #include <algorithm>
 
-#include "common.hpp"
+#include "plane_table.hpp"
 
 namespace {
 
-constexpr int kMaxPlanesC = 96;     // planes per launch (32 YUV frames)
 constexpr int kSlab = 65535;        // samples per histogram workgroup: a packed u16 counter never overflows into its neighbour
 constexpr int kHistThreads = 1024;
 constexpr int kInterpThreads = 256;
@@ -39,22 +38,7 @@ struct CPlane {
     int lds;      // 8-bit interpolation: LUTs through LDS
 };
 
-struct CParams {
-    CPlane p[kMaxPlanesC];
-    int nplanes;
-};
-
-__device__ __forceinline__ int find_plane(const CParams &prm, int b, int CPlane::*first) {
-    int pi = 0, hi = prm.nplanes - 1;
-    while (pi < hi) {
-        const int mid = (pi + hi + 1) >> 1;
-        if (b >= prm.p[mid].*first)
-            pi = mid;
-        else
-            hi = mid - 1;
-    }
-    return pi;
-}
+typedef PlaneTable<CPlane, 96> CParams;  // 96 planes per launch (32 YUV frames)
 
 template <typename T>
 struct Hist;
@@ -99,7 +83,7 @@ __global__ __launch_bounds__(kHistThreads) void clahe_hist_kernel(const CParams 
     typedef T VecT __attribute__((ext_vector_type(V)));
     __shared__ __attribute__((aligned(16))) uint32_t h[Hist<T>::kWords];
     const int b = blockIdx.x;
-    const CPlane &pl = prm.p[find_plane(prm, b, &CPlane::hb0)];
+    const CPlane &pl = prm.p[vszip_find_plane(prm, b, &CPlane::hb0)];
     const int local = b - pl.hb0;
     const int tile = local / pl.sper, slab = local - tile * pl.sper;
     const int tyi = tile / pl.tx, txi = tile - tyi * pl.tx;
@@ -158,7 +142,7 @@ __global__ __launch_bounds__(NT) void clahe_lut_kernel(const CParams prm) {
     __shared__ uint32_t red[NW];
     __shared__ uint32_t wsum[NW];
     const int b = blockIdx.x;
-    const CPlane &pl = prm.p[find_plane(prm, b, &CPlane::lb0)];
+    const CPlane &pl = prm.p[vszip_find_plane(prm, b, &CPlane::lb0)];
     const int tile = b - pl.lb0;
     const uint32_t *g = pl.hist + (size_t)tile * HS + threadIdx.x * BPT;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -250,7 +234,7 @@ __global__ __launch_bounds__(kInterpThreads) void clahe_interp_kernel(const CPar
     typedef T VecT __attribute__((ext_vector_type(V)));
     __shared__ __attribute__((aligned(16))) uint8_t lds[sizeof(T) == 1 ? kLdsLutBytes : 16];
     const int b = blockIdx.x;
-    const CPlane &pl = prm.p[find_plane(prm, b, &CPlane::ib0)];
+    const CPlane &pl = prm.p[vszip_find_plane(prm, b, &CPlane::ib0)];
     const int y0 = (b - pl.ib0) * R;
     const T *src = static_cast<const T *>(pl.src);
     T *dst = static_cast<T *>(pl.dst);
@@ -343,7 +327,7 @@ int run(vszip_ctx *ctx, const vszip_plane *planes, int nplanes, uint32_t limit, 
     // the table has the same number of tiles, hence the same storage.
     const size_t cap = (size_t)std::max(ctx->opt.clahe_scratch_mib, 1) << 20;
     const size_t hbytes = (size_t)tiles_x * tiles_y * HS * 4, lbytes = (size_t)tiles_x * tiles_y * HS * sizeof(T);
-    const int per_group = (int)std::max<size_t>(1, std::min<size_t>(kMaxPlanesC, cap / (hbytes + lbytes)));
+    const int per_group = (int)std::max<size_t>(1, std::min<size_t>(CParams::capacity, cap / (hbytes + lbytes)));
     const int gmax = std::min(per_group, nplanes);
     const size_t need = (hbytes + lbytes) * (size_t)gmax;  // [histograms of the group][LUTs of the group]
     int rc = vszip_ensure_scratch(ctx, need);

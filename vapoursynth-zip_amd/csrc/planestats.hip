@@ -12,7 +12,7 @@
 // of the high byte, the two buckets the thresholds fall into are located on the device,
 // and a second sweep histograms the low byte inside those two buckets. Integer results
 // are exact; float sums differ from the reference's sequential f64 order by rounding only.
-#include "common.hpp"
+#include "plane_table.hpp"
 #include <cstring>
 #include <functional>
 #include <type_traits>
@@ -20,7 +20,6 @@
 namespace {
 
 constexpr int kThreads = 256;
-constexpr int kMaxPlanesPS = 192;  // planes per launch (the per-plane table travels in the kernel argument: 7.7 KB): 64 YUV frames are ONE launch (round 4; 48 before)
 constexpr int kHistWords = 4096, kBucketWords = 16;
 // thresholded PlaneMinMax, single-read sweep: the candidate ranges (see hist_sweep_kernel MODE 1). Round 6, tools/minmax_thr_timing.py (64 x 4K YUV420P16 a call,
 // k frames/s on noise / the test picture / the picture x 257; two sweeps: 93 on all three): 1280 values x 4 copies (round 3's, sized for a row sample's error)
@@ -48,7 +47,7 @@ struct PSPlane {
 constexpr int kMaxExclude = 256;  // distinct exclude values per call (the list travels in the kernel argument)
 
 struct PSParams {
-    PSPlane p[kMaxPlanesPS];
+    PSPlane p[kPlanesPerLaunch];
     int nplanes;
     int rows_per_block;
     int32_t excl[kMaxExclude];
@@ -144,18 +143,6 @@ __device__ __forceinline__ void row_apply(const T *s, const T *r, int w, F &&fn)
     for (int x = x0 + (int)threadIdx.x; x < w; x += kThreads) fn(s[x], REF ? r[x] : s[x]);
 }
 
-__device__ __forceinline__ int find_plane(const PSParams &prm, int b) {  // (block0 ascends: eight scalar steps for 192 planes)
-    int lo = 0, hi = prm.nplanes - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (b >= prm.p[mid].block0)
-            lo = mid;
-        else
-            hi = mid - 1;
-    }
-    return lo;
-}
-
 // ---- PlaneAverage ---------------------------------------------------------------
 // NEX: compile-time size of the exclude list (0, 1, 2, 4 or 8 entries; a list shorter than NEX is
 // padded with copies of its first entry by the host) — the common exclude=[-1] on an integer
@@ -168,7 +155,7 @@ __global__ __launch_bounds__(kThreads) void average_kernel(const PSParams prm) {
     __shared__ Acc sh[8];
     __shared__ uint32_t shc[8];
     const int b = blockIdx.x;
-    const PSPlane pl = prm.p[find_plane(prm, b)];
+    const PSPlane pl = prm.p[vszip_find_plane(prm, b)];
     const int y0 = (b - pl.block0) * prm.rows_per_block;
     const int y1 = min(y0 + prm.rows_per_block, pl.h);
     const T *src = static_cast<const T *>(pl.src);
@@ -274,7 +261,7 @@ __global__ __launch_bounds__(kThreads) void minmax_kernel(const PSParams prm) {
     __shared__ double shd[8];
     __shared__ float shmin[8], shmax[8];
     const int b = blockIdx.x;
-    const PSPlane pl = prm.p[find_plane(prm, b)];
+    const PSPlane pl = prm.p[vszip_find_plane(prm, b)];
     const int y0 = (b - pl.block0) * prm.rows_per_block;
     const int y1 = min(y0 + prm.rows_per_block, pl.h);
     const T *src = static_cast<const T *>(pl.src);
@@ -742,7 +729,7 @@ __global__ __launch_bounds__(kSweepThreads) void hist_sweep_kernel(const PSParam
     const int u1 = (int)((long)(blockIdx.x + 1) * units_total / gridDim.x);
     int u = (int)((long)blockIdx.x * units_total / gridDim.x);
     while (u < u1) {  // one turn per plane the range touches (workgroup-uniform)
-        const int pi = find_plane(prm, u);
+        const int pi = vszip_find_plane(prm, u);
         const PSPlane pl = prm.p[pi];
         const int ue = min(u1, pl.block0 + pl.nblocks);
         uint32_t *bk = prm.bucket + pi * kBucketWords;
@@ -1027,7 +1014,7 @@ struct Launch {
 
 int prepare(vszip_ctx *ctx, const vszip_plane *planes, int nplanes, bool need_ref, Launch &L, double *result_dev) {
     if (!ctx || !planes || nplanes <= 0) return VSZIP_ERR_ARG;
-    if (nplanes > kMaxPlanesPS) return vszip_set_error(ctx, VSZIP_ERR_ARG, "at most %d planes per call", kMaxPlanesPS);
+    if (nplanes > kPlanesPerLaunch) return vszip_set_error(ctx, VSZIP_ERR_ARG, "at most %d planes per call", kPlanesPerLaunch);
     PSParams &prm = L.prm;
     prm.nplanes = nplanes;
     int rows = 8;
@@ -1172,7 +1159,7 @@ int run_minmax_t(vszip_ctx *ctx, Launch &L, bool no_thr, int batch, std::functio
     if (wide && !no_thr && !ctx->opt.minmax_no_predict && batch >= 0) {
         // kPredSlots tables per plane group, by signature, least recently used replaced: the thresholded statistics of several clips (or one clip under
         // several thresholds) of a filter graph arrive interleaved on one context, and each keeps its own predictions
-        const size_t group = (size_t)batch * kPredSlots, need = (group + kPredSlots) * kMaxPlanesPS;
+        const size_t group = (size_t)batch * kPredSlots, need = (group + kPredSlots) * kPlanesPerLaunch;
         if (ctx->minmax_pred_planes < need) {  // grow-only, old predictions kept (a group's tables do not move when later groups are added)
             const size_t cap = std::max<size_t>(need, 2 * ctx->minmax_pred_planes);
             void *np = nullptr;
@@ -1201,7 +1188,7 @@ int run_minmax_t(vszip_ctx *ctx, Launch &L, bool no_thr, int batch, std::functio
         }
         ctx->minmax_sig[slot] = sig;  // (this call leaves predictions for the next one of its signature, whichever way it runs)
         ctx->minmax_used[slot] = ++ctx->minmax_tick;
-        L.prm.pred = static_cast<uint32_t *>(ctx->minmax_pred) + slot * kMaxPlanesPS * 2;
+        L.prm.pred = static_cast<uint32_t *>(ctx->minmax_pred) + slot * kPlanesPerLaunch * 2;
         if (predicted) ++ctx->minmax_predicted;
     } else {
         L.prm.pred = nullptr;
@@ -1335,21 +1322,21 @@ static int plane_minmax_batch(vszip_ctx *ctx, int dtype, const vszip_plane *plan
     return rc;
 }
 
-// Any number of planes per call: batches of kMaxPlanesPS (the per-plane table travels in the kernel argument).
-// Every group of kMaxPlanesPS planes is queued without waiting for the one before (their results land in different entries of the
+// Any number of planes per call: batches of kPlanesPerLaunch (the per-plane table travels in the kernel argument).
+// Every group of kPlanesPerLaunch planes is queued without waiting for the one before (their results land in different entries of the
 // result array; the scratch tables are reused in stream order): a 64-frame call is four groups and ONE synchronise.
 static int plane_average_queue(vszip_ctx *ctx, int dtype, const vszip_plane *planes, int nplanes, const int32_t *exclude, int nexclude, int bits_per_sample, double *result_dev) {
-    for (int o = 0; o < nplanes; o += kMaxPlanesPS) {
-        const int rc = plane_average_batch(ctx, dtype, planes + o, std::min(kMaxPlanesPS, nplanes - o), exclude, nexclude, bits_per_sample, result_dev + (size_t)o * 4);
+    for (int o = 0; o < nplanes; o += kPlanesPerLaunch) {
+        const int rc = plane_average_batch(ctx, dtype, planes + o, std::min(kPlanesPerLaunch, nplanes - o), exclude, nexclude, bits_per_sample, result_dev + (size_t)o * 4);
         if (rc != VSZIP_OK) return rc;
     }
     return VSZIP_OK;
 }
 static int plane_minmax_queue(vszip_ctx *ctx, int dtype, const vszip_plane *planes, int nplanes, float minthr, float maxthr, int bits_per_sample, double *result_dev,
                               std::function<int()> *deferred = nullptr) {
-    if (nplanes > kMaxPlanesPS) deferred = nullptr;  // (the groups share the scratch tables in stream order: a later group's sweep wipes what a deferred fallback needs)
-    for (int o = 0; o < nplanes; o += kMaxPlanesPS) {
-        const int rc = plane_minmax_batch(ctx, dtype, planes + o, std::min(kMaxPlanesPS, nplanes - o), minthr, maxthr, bits_per_sample, result_dev + (size_t)o * 4, o / kMaxPlanesPS, deferred);
+    if (nplanes > kPlanesPerLaunch) deferred = nullptr;  // (the groups share the scratch tables in stream order: a later group's sweep wipes what a deferred fallback needs)
+    for (int o = 0; o < nplanes; o += kPlanesPerLaunch) {
+        const int rc = plane_minmax_batch(ctx, dtype, planes + o, std::min(kPlanesPerLaunch, nplanes - o), minthr, maxthr, bits_per_sample, result_dev + (size_t)o * 4, o / kPlanesPerLaunch, deferred);
         if (rc != VSZIP_OK) return rc;
     }
     return VSZIP_OK;
