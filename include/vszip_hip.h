@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define VSZIP_ABI_VERSION 4 /* additive since 4: vszip_clahe; 4 (round 5): vszip_dev_alloc searches a bounded number of candidates and keeps nothing (below); vszip_dev_arena_info added; vszip_dev_trim, vszip_dev_placement_info and
+#define VSZIP_ABI_VERSION 4 /* additive since 4: vszip_clahe, vszip_comb_mask, vszip_comb_mask_mt; 4 (round 5): vszip_dev_alloc searches a bounded number of candidates and keeps nothing (below); vszip_dev_arena_info added; vszip_dev_trim, vszip_dev_placement_info and
                                vszip_dev_alloc_probed removed (nothing is searched for or parked any more); 3 (round 4): vszip_ctx_set_option / _get_option, vszip_dev_probe_region,
                                vszip_plane_average_async, vszip_plane_minmax_async added; 2 (round 3): vszip_ssim_source grew (YUV sources); entry points added since 1:
                                vszip_chain_run, vszip_ssimulacra2_src, vszip_to_rgbs_linear, vszip_probe_read_each, vszip_resample_table */
@@ -118,7 +118,8 @@ int vszip_probe_read_each(vszip_ctx *ctx, double *total_ms, int *launches, float
  *
  * Plane memory: what a call reads and writes. Valid for every entry point that takes planes: the vszip_plane table calls
  * and the pointer-array calls (vszip_ssimulacra2 / _src, vszip_to_rgbs_linear, vszip_xpsnr_wsse / _batch, the sclips /
- * mclips of vszip_eedi3 / _mclip, vszip_limit_filter's refs, vszip_adaptive_binarize's second clip in `ref`). A plane is
+ * mclips of vszip_eedi3 / _mclip, vszip_limit_filter's refs, vszip_adaptive_binarize's second clip and vszip_comb_mask's
+ * previous frame in `ref`). A plane is
  * (pointer, stride, w, h) with stride >= w. Derived from the kernels ("Furthest read of every
  * kernel") and kept by tests/test_gpu_footprint.py.
  *
@@ -145,7 +146,9 @@ int vszip_probe_read_each(vszip_ctx *ctx, double *total_ms, int *launches, float
  *    be the flt plane, the source plane or refs[i]) and vszip_adaptive_binarize (dst may be either clip), whose every
  *    output sample depends on the input samples at the same position only, and for vszip_clahe (the histograms are
  *    complete before the first store). Every other filter reads neighbourhoods: dst must not overlap any input, and
- *    two output planes of one call must not overlap each other. Partial overlap is never allowed.
+ *    two output planes of one call must not overlap each other; vszip_comb_mask and vszip_comb_mask_mt are of this kind
+ *    (rows above and below, and the previous frame's plane in `ref`): their dst must overlap neither src nor ref, while
+ *    ref may be the very src pointer. Partial overlap is never allowed.
  */
 typedef struct vszip_plane {
     const void *src; /* input plane */
@@ -231,6 +234,28 @@ int vszip_adaptive_binarize(vszip_ctx *ctx, const vszip_plane *planes, int nplan
  * context's scratch (grow-only), at most VSZIP_CLAHE_SCRATCH_MIB of it per plane group (csrc/options.inc).
  */
 int vszip_clahe(vszip_ctx *ctx, int dtype, const vszip_plane *planes, int nplanes, uint32_t limit, int tiles_x, int tiles_y);
+
+/*
+ * CombMask — replaces filter.process (src/filters/comb_mask.zig:18-47: metric0Mask :49, metric1Mask :101, motionMaskAnd :142,
+ * expandMask :180) as called per plane by CombMask(metric_1, expand, motion).getFrame (src/vapoursynth/comb_mask.zig:22-61).
+ * 8-bit planes, each with its own size (h >= 3). planes[i].src is the plane of frame n, planes[i].dst the mask (255 / 0);
+ * planes[i].ref is the same plane of frame max(0, n - 1): required when mthresh > 0 (it may be the very src pointer, as for
+ * frame 0: the mask is then all zero), ignored when mthresh == 0. cthresh, mthresh, expand, metric are the wrapper's arguments
+ * (defaults 6, 9, 1, 0). One fused pass: no intermediate plane, no scratch. Asynchronous on the context stream.
+ * VSZIP_ERR_ARG, with the wrapper's create-time wording in vszip_last_error (comb_mask.zig(vs):93-120): cthresh outside
+ * 0..255 (metric 0) or 0..65025 (metric 1), mthresh outside 0..255, a plane with fewer than 3 rows; and a NULL src or dst,
+ * or a NULL ref with mthresh > 0. Only [0, w) x h of dst is written ("Plane memory"; the reference also writes pitch padding).
+ */
+int vszip_comb_mask(vszip_ctx *ctx, const vszip_plane *planes, int nplanes, int cthresh, int mthresh, int expand, int metric);
+
+/*
+ * CombMaskMT — replaces filter.process (src/filters/comb_mask_mt.zig:11-66) as called per plane by CombMaskMT(same_thr).getFrame
+ * (src/vapoursynth/comb_mask_mt.zig:22-59). 8-bit planes (h >= 3): rows 0 and h - 1 are 0; elsewhere p = (up - s) * (down - s)
+ * gives 255 where p > thY2, 0 where p < thY1 (thY1 == thY2: where p <= thY2) and min((p - thY1) * 256 / (thY2 - thY1), 255) in
+ * between. `ref` is not used. Asynchronous. VSZIP_ERR_ARG with the wrapper's wording (comb_mask_mt.zig(vs):87-110): thY1 or thY2
+ * outside [0;255], thY1 > thY2, a plane with fewer than 3 rows; and a NULL src or dst.
+ */
+int vszip_comb_mask_mt(vszip_ctx *ctx, const vszip_plane *planes, int nplanes, int thy1, int thy2);
 
 /*
  * PlaneMinMax — replaces filter.minMax / minMaxRef / minMaxNoThr / minMaxNoThrRef

@@ -120,6 +120,8 @@ SYMBOLS = {
     "vszip_limit_filter": (_i, [_vp, _i, _PP, C.POINTER(_vp), C.POINTER(_pd), _i, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "vszip_adaptive_binarize": (_i, [_vp, _PP, _i, _i]),
     "vszip_clahe": (_i, [_vp, _i, _PP, _i, C.c_uint32, _i, _i]),
+    "vszip_comb_mask": (_i, [_vp, _PP, _i, _i, _i, _i, _i]),
+    "vszip_comb_mask_mt": (_i, [_vp, _PP, _i, _i, _i]),
     "vszip_plane_average": (_i, [_vp, _i, _PP, _i, C.POINTER(C.c_int32), _i, _i, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "vszip_plane_minmax": (_i, [_vp, _i, _PP, _i, C.c_float, C.c_float, _i, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "vszip_plane_average_async": (_i, [_vp, _i, _PP, _i, C.POINTER(C.c_int32), _i, _i, _vp]),
@@ -463,6 +465,30 @@ class Device:
         table = self.plane_table(srcs, dsts)
         dt, fn, ctx, check, lim = _NP2DT[srcs[0].dtype], self.lib.vszip_clahe, self.ctx, self.check, int(limit)
         return lambda: check(fn(ctx, dt, table, n, lim, tx, ty))
+
+    def comb_mask(self, srcs, dsts, prevs=None, cthresh=6, mthresh=9, expand=True, metric=0):
+        """vszip.CombMask on every plane of srcs (u8, any sizes, at least 3 rows): dsts[i] = 255 / 0. prevs[i]: the same plane of the
+        previous frame (frame 0: srcs[i] itself), needed when mthresh > 0."""
+        table = self.plane_table(srcs, dsts, prevs)
+        self.check(self.lib.vszip_comb_mask(self.ctx, table, len(srcs), int(cthresh), int(mthresh), int(bool(expand)), int(metric)))
+
+    def prepared_comb_mask(self, srcs, dsts, prevs=None, cthresh=6, mthresh=9, expand=True, metric=0):
+        """-> a callable queueing vszip_comb_mask on argument blocks built once."""
+        n = len(srcs)
+        table = self.plane_table(srcs, dsts, prevs)
+        fn, ctx, check, args = self.lib.vszip_comb_mask, self.ctx, self.check, (int(cthresh), int(mthresh), int(bool(expand)), int(metric))
+        return lambda: check(fn(ctx, table, n, *args))
+
+    def comb_mask_mt(self, srcs, dsts, thY1=30, thY2=30):
+        """vszip.CombMaskMT on every plane of srcs (u8, at least 3 rows)."""
+        self.check(self.lib.vszip_comb_mask_mt(self.ctx, self.plane_table(srcs, dsts), len(srcs), int(thY1), int(thY2)))
+
+    def prepared_comb_mask_mt(self, srcs, dsts, thY1=30, thY2=30):
+        """-> a callable queueing vszip_comb_mask_mt on argument blocks built once."""
+        n = len(srcs)
+        table = self.plane_table(srcs, dsts)
+        fn, ctx, check, a, b = self.lib.vszip_comb_mask_mt, self.ctx, self.check, int(thY1), int(thY2)
+        return lambda: check(fn(ctx, table, n, a, b))
 
     def prepared_limit_filter(self, flts, srcs, dsts, dark_thr, bright_thr, elast):
         """-> a callable queueing vszip_limit_filter (no third clip) on argument blocks built once."""
