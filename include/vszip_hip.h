@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define VSZIP_ABI_VERSION 4 /* additive since 4: vszip_clahe, vszip_comb_mask, vszip_comb_mask_mt; 4 (round 5): vszip_dev_alloc searches a bounded number of candidates and keeps nothing (below); vszip_dev_arena_info added; vszip_dev_trim, vszip_dev_placement_info and
+#define VSZIP_ABI_VERSION 4 /* additive since 4: vszip_clahe, vszip_comb_mask, vszip_comb_mask_mt, vszip_checkmate; 4 (round 5): vszip_dev_alloc searches a bounded number of candidates and keeps nothing (below); vszip_dev_arena_info added; vszip_dev_trim, vszip_dev_placement_info and
                                vszip_dev_alloc_probed removed (nothing is searched for or parked any more); 3 (round 4): vszip_ctx_set_option / _get_option, vszip_dev_probe_region,
                                vszip_plane_average_async, vszip_plane_minmax_async added; 2 (round 3): vszip_ssim_source grew (YUV sources); entry points added since 1:
                                vszip_chain_run, vszip_ssimulacra2_src, vszip_to_rgbs_linear, vszip_probe_read_each, vszip_resample_table */
@@ -118,8 +118,9 @@ int vszip_probe_read_each(vszip_ctx *ctx, double *total_ms, int *launches, float
  *
  * Plane memory: what a call reads and writes. Valid for every entry point that takes planes: the vszip_plane table calls
  * and the pointer-array calls (vszip_ssimulacra2 / _src, vszip_to_rgbs_linear, vszip_xpsnr_wsse / _batch, the sclips /
- * mclips of vszip_eedi3 / _mclip, vszip_limit_filter's refs, vszip_adaptive_binarize's second clip and vszip_comb_mask's
- * previous frame in `ref`). A plane is
+ * mclips of vszip_eedi3 / _mclip, vszip_limit_filter's refs, vszip_adaptive_binarize's second clip, vszip_comb_mask's
+ * previous frame in `ref` and the neighbouring frames' planes of vszip_checkmate's vszip_temporal_nbrs, which are inputs
+ * under clauses 1-3 with the size of the entry's plane and pitches of their own: h x stride readable each). A plane is
  * (pointer, stride, w, h) with stride >= w. Derived from the kernels ("Furthest read of every
  * kernel") and kept by tests/test_gpu_footprint.py.
  *
@@ -148,7 +149,10 @@ int vszip_probe_read_each(vszip_ctx *ctx, double *total_ms, int *launches, float
  *    complete before the first store). Every other filter reads neighbourhoods: dst must not overlap any input, and
  *    two output planes of one call must not overlap each other; vszip_comb_mask and vszip_comb_mask_mt are of this kind
  *    (rows above and below, and the previous frame's plane in `ref`): their dst must overlap neither src nor ref, while
- *    ref may be the very src pointer. Partial overlap is never allowed.
+ *    ref may be the very src pointer. vszip_checkmate likewise: any of its four neighbour planes may be the very src pointer
+ *    or each other (what clamping frame indices to the clip produces at its ends), dst must overlap no input, and only
+ *    [0, w) x h of dst is written (the reference copies two whole pitches at either end of a plane, padding included; this
+ *    library does not). Partial overlap is never allowed.
  */
 typedef struct vszip_plane {
     const void *src; /* input plane */
@@ -256,6 +260,29 @@ int vszip_comb_mask(vszip_ctx *ctx, const vszip_plane *planes, int nplanes, int 
  * outside [0;255], thY1 > thY2, a plane with fewer than 3 rows; and a NULL src or dst.
  */
 int vszip_comb_mask_mt(vszip_ctx *ctx, const vszip_plane *planes, int nplanes, int thy1, int thy2);
+
+/*
+ * Checkmate — replaces filter.process (src/filters/checkmate.zig:5-57) and the row loop around it in Checkmate(use_tthr2).getFrame
+ * (src/vapoursynth/checkmate.zig:26-96). The first filter here whose frame n reads up to five frames: planes[i].src is the plane
+ * of frame n, planes[i].dst the output (`ref` is not used), and nbrs[i] names the same plane of frames n - 2 .. n + 2, each
+ * with its own pitch, the frame indices already clamped to the clip as getFrame does (max(0, n - k), min(n + k, frames - 1)):
+ * at a clip's ends they are the src pointer itself or each other. p2 and n2 are read only when tthr2 > 0 and may be NULL
+ * otherwise. 8-bit planes, each with its own size (w >= 3, h >= 5), so the planes of a whole clip fit in one call with the
+ * clip's own frames as each other's neighbours. Rows 0, 1, h - 2, h - 1 are copies of src; elsewhere the output blends the
+ * sample with a sharpened version of itself (rows y - 2, y, y + 2, columns x - 2, x, x + 2 clamped to the plane) and with frames
+ * n - 1 and n + 1, weighted by how little the column sums differ (thr, tmax; defaults 12, 12), or, with tthr2 > 0 (default 0)
+ * and all of |p1 - n1|, |p2 - src|, |src - n2| below tthr2, is (p1 + 2 src + n1) >> 2. One fused pass: no intermediate plane, no
+ * scratch. Asynchronous on the context stream. VSZIP_ERR_ARG, with the wrapper's create-time wording in vszip_last_error
+ * (checkmate.zig(vs):125-153, in its order): tmax outside [1;255], tthr2 negative, thr outside [0;255], a plane narrower than 3
+ * or shorter than 5; and a NULL src, dst, p1 or n1, or a NULL p2 or n2 with tthr2 > 0.
+ */
+typedef struct vszip_temporal_nbrs { /* the same plane of the neighbouring frames, already clamped to the clip by the caller */
+    const void *p2, *p1, *n1, *n2;   /* frames n-2, n-1, n+1, n+2; p2 / n2 ignored (may be NULL) when the filter does not use them */
+    ptrdiff_t p2_stride, p1_stride, n1_stride, n2_stride;
+} vszip_temporal_nbrs;
+
+int vszip_checkmate(vszip_ctx *ctx, const vszip_plane *planes, const vszip_temporal_nbrs *nbrs, int nplanes,
+                    int thr, int tmax, int tthr2);
 
 /*
  * PlaneMinMax — replaces filter.minMax / minMaxRef / minMaxNoThr / minMaxNoThrRef

@@ -37,6 +37,14 @@ class Plane(C.Structure):
     ]
 
 
+class TemporalNbrs(C.Structure):
+    """vszip_temporal_nbrs"""
+    _fields_ = [
+        ("p2", C.c_void_p), ("p1", C.c_void_p), ("n1", C.c_void_p), ("n2", C.c_void_p),
+        ("p2_stride", C.c_ssize_t), ("p1_stride", C.c_ssize_t), ("n1_stride", C.c_ssize_t), ("n2_stride", C.c_ssize_t),
+    ]
+
+
 class BilateralCfg(C.Structure):
     _fields_ = [
         ("sigmaS", C.c_double), ("sigmaR", C.c_double), ("process", C.c_int32), ("algorithm", C.c_int32),
@@ -122,6 +130,7 @@ SYMBOLS = {
     "vszip_clahe": (_i, [_vp, _i, _PP, _i, C.c_uint32, _i, _i]),
     "vszip_comb_mask": (_i, [_vp, _PP, _i, _i, _i, _i, _i]),
     "vszip_comb_mask_mt": (_i, [_vp, _PP, _i, _i, _i]),
+    "vszip_checkmate": (_i, [_vp, _PP, C.POINTER(TemporalNbrs), _i, _i, _i, _i]),
     "vszip_plane_average": (_i, [_vp, _i, _PP, _i, C.POINTER(C.c_int32), _i, _i, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "vszip_plane_minmax": (_i, [_vp, _i, _PP, _i, C.c_float, C.c_float, _i, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "vszip_plane_average_async": (_i, [_vp, _i, _PP, _i, C.POINTER(C.c_int32), _i, _i, _vp]),
@@ -489,6 +498,48 @@ class Device:
         table = self.plane_table(srcs, dsts)
         fn, ctx, check, a, b = self.lib.vszip_comb_mask_mt, self.ctx, self.check, int(thY1), int(thY2)
         return lambda: check(fn(ctx, table, n, a, b))
+
+    @staticmethod
+    def temporal_nbrs(p1s, n1s, p2s=None, n2s=None):
+        """-> the vszip_temporal_nbrs array of a plane table: the same plane of frames n - 1, n + 1 (and n - 2, n + 2), already clamped"""
+        arr = (TemporalNbrs * len(p1s))()
+        for i in range(len(p1s)):
+            arr[i].p1, arr[i].p1_stride, arr[i].n1, arr[i].n1_stride = p1s[i].ptr, p1s[i].stride, n1s[i].ptr, n1s[i].stride
+            if p2s is not None and p2s[i] is not None:
+                arr[i].p2, arr[i].p2_stride = p2s[i].ptr, p2s[i].stride
+            if n2s is not None and n2s[i] is not None:
+                arr[i].n2, arr[i].n2_stride = n2s[i].ptr, n2s[i].stride
+        return arr
+
+    def checkmate(self, srcs, dsts, p1s, n1s, p2s=None, n2s=None, thr=12, tmax=12, tthr2=0):
+        """vszip.Checkmate on every plane of srcs (u8, any sizes, at least 3 x 5): p1s / n1s (and, for tthr2 > 0, p2s / n2s) are the same
+        planes of the neighbouring frames, clamped to the clip (they may be srcs[i] itself)."""
+        self.check(self.lib.vszip_checkmate(self.ctx, self.plane_table(srcs, dsts), self.temporal_nbrs(p1s, n1s, p2s, n2s), len(srcs), int(thr), int(tmax), int(tthr2)))
+
+    def prepared_checkmate(self, srcs, dsts, p1s, n1s, p2s=None, n2s=None, thr=12, tmax=12, tthr2=0):
+        """-> a callable queueing vszip_checkmate on argument blocks built once."""
+        n = len(srcs)
+        table, nbrs = self.plane_table(srcs, dsts), self.temporal_nbrs(p1s, n1s, p2s, n2s)
+        fn, ctx, check, args = self.lib.vszip_checkmate, self.ctx, self.check, (int(thr), int(tmax), int(tthr2))
+        return lambda: check(fn(ctx, table, nbrs, n, *args))
+
+    @staticmethod
+    def clip_neighbours(frames):
+        """frames[f]: the planes of frame f -> flat (srcs, p1s, n1s, p2s, n2s) over all planes of the clip, frame indices clamped as the
+        wrapper's getFrame does: max(0, n - k), min(n + k, frames - 1)"""
+        last = len(frames) - 1
+        pick = lambda off: [p for f in range(len(frames)) for p in frames[min(max(f + off, 0), last)]]
+        return pick(0), pick(-1), pick(1), pick(-2), pick(2)
+
+    def prepared_checkmate_clip(self, frames, dsts, thr=12, tmax=12, tthr2=0):
+        """-> a callable queueing checkmate_clip on argument blocks built once."""
+        srcs, p1s, n1s, p2s, n2s = self.clip_neighbours(frames)
+        return self.prepared_checkmate(srcs, [p for f in dsts for p in f], p1s, n1s, p2s, n2s, thr, tmax, tthr2)
+
+    def checkmate_clip(self, frames, dsts, thr=12, tmax=12, tthr2=0):
+        """vszip.Checkmate on a whole resident clip: frames[f] / dsts[f] are the device planes of frame f. One vszip_checkmate over
+        all planes of the clip; a frame's neighbours are the clip's other frames (nothing is copied)."""
+        self.prepared_checkmate_clip(frames, dsts, thr, tmax, tthr2)()
 
     def prepared_limit_filter(self, flts, srcs, dsts, dark_thr, bright_thr, elast):
         """-> a callable queueing vszip_limit_filter (no third clip) on argument blocks built once."""
