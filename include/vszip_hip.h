@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define VSZIP_ABI_VERSION 4 /* additive since 4: vszip_clahe, vszip_comb_mask, vszip_comb_mask_mt, vszip_checkmate; 4 (round 5): vszip_dev_alloc searches a bounded number of candidates and keeps nothing (below); vszip_dev_arena_info added; vszip_dev_trim, vszip_dev_placement_info and
+#define VSZIP_ABI_VERSION 4 /* additive since 4: vszip_clahe, vszip_comb_mask, vszip_comb_mask_mt, vszip_checkmate, vszip_mosquito_nr; 4 (round 5): vszip_dev_alloc searches a bounded number of candidates and keeps nothing (below); vszip_dev_arena_info added; vszip_dev_trim, vszip_dev_placement_info and
                                vszip_dev_alloc_probed removed (nothing is searched for or parked any more); 3 (round 4): vszip_ctx_set_option / _get_option, vszip_dev_probe_region,
                                vszip_plane_average_async, vszip_plane_minmax_async added; 2 (round 3): vszip_ssim_source grew (YUV sources); entry points added since 1:
                                vszip_chain_run, vszip_ssimulacra2_src, vszip_to_rgbs_linear, vszip_probe_read_each, vszip_resample_table */
@@ -152,7 +152,10 @@ int vszip_probe_read_each(vszip_ctx *ctx, double *total_ms, int *launches, float
  *    ref may be the very src pointer. vszip_checkmate likewise: any of its four neighbour planes may be the very src pointer
  *    or each other (what clamping frame indices to the clip produces at its ends), dst must overlap no input, and only
  *    [0, w) x h of dst is written (the reference copies two whole pitches at either end of a plane, padding included; this
- *    library does not). Partial overlap is never allowed.
+ *    library does not). vszip_mosquito_nr reads a 9 x 9 neighbourhood: clauses 1-4 hold, its dst must not overlap src (for a
+ *    plane with strength 0, which is copied, too), bases and pitches that are not multiples of four samples take a slower
+ *    path with the same bits, and integer samples above 2^bits - 1 are not an error: they are processed as the reference
+ *    would process them and the result is clamped to 2^bits - 1. Partial overlap is never allowed.
  */
 typedef struct vszip_plane {
     const void *src; /* input plane */
@@ -283,6 +286,23 @@ typedef struct vszip_temporal_nbrs { /* the same plane of the neighbouring frame
 
 int vszip_checkmate(vszip_ctx *ctx, const vszip_plane *planes, const vszip_temporal_nbrs *nbrs, int nplanes,
                     int thr, int tmax, int tthr2);
+
+/*
+ * MosquitoNR — replaces MosquitoNR(T).process (src/filters/mosquito_nr.zig:264-386: the padding :297-326, smooth :31-162, fwdV / fwdH /
+ * invH / invV :164-262, the LL mix :353-360, the store :366-385) and MosquitoNRFloat.process (src/filters/mosquito_nr_float.zig:263-369)
+ * as called per plane by Filter(T).getFrame (src/vapoursynth/mosquito_nr.zig:30-82). dtype VSZIP_U8 (bits_per_sample 8), VSZIP_U16
+ * (9..16) or VSZIP_F32 (bits_per_sample is ignored); one dtype per call, any number of planes of any sizes (at least 4 x 4), so the
+ * planes of many frames fit in one call. strength[i] (0..32; the wrapper's default 16), restore[i] (0..128; 128) and radius[i] (1 or
+ * 2; 2) belong to planes[i]; chroma[i] != 0 clamps a float plane to [-0.5, 0.5] instead of [0, 1] (the wrapper passes plane > 0), NULL
+ * means all luma, and it is ignored for integers. `ref` is not used. A plane with strength 0 is copied ([0, w) x h only). One fused
+ * pass: the nine passes and eleven scratch planes of the reference happen in LDS, tile by tile; no scratch. Bit-exact with the
+ * reference in all three sample types, float included. Asynchronous on the context stream. VSZIP_ERR_ARG, with the wrapper's wording in
+ * vszip_last_error (mosquito_nr.zig(vs):99-134, in its order): a dtype / bits_per_sample combination outside the list, a plane narrower
+ * or shorter than 4, and strength, restore or radius out of range with hz.getArray's texts ("MosquitoNR: strength value 33 is above
+ * maximum 32."); and a NULL parameter array, src or dst.
+ */
+int vszip_mosquito_nr(vszip_ctx *ctx, int dtype, int bits_per_sample, const vszip_plane *planes, int nplanes,
+                      const int32_t *strength, const int32_t *restore, const int32_t *radius, const uint8_t *chroma);
 
 /*
  * PlaneMinMax — replaces filter.minMax / minMaxRef / minMaxNoThr / minMaxNoThrRef

@@ -131,6 +131,7 @@ SYMBOLS = {
     "vszip_comb_mask": (_i, [_vp, _PP, _i, _i, _i, _i, _i]),
     "vszip_comb_mask_mt": (_i, [_vp, _PP, _i, _i, _i]),
     "vszip_checkmate": (_i, [_vp, _PP, C.POINTER(TemporalNbrs), _i, _i, _i, _i]),
+    "vszip_mosquito_nr": (_i, [_vp, _i, _i, _PP, _i, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_uint8)]),
     "vszip_plane_average": (_i, [_vp, _i, _PP, _i, C.POINTER(C.c_int32), _i, _i, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "vszip_plane_minmax": (_i, [_vp, _i, _PP, _i, C.c_float, C.c_float, _i, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "vszip_plane_average_async": (_i, [_vp, _i, _PP, _i, C.POINTER(C.c_int32), _i, _i, _vp]),
@@ -540,6 +541,31 @@ class Device:
         """vszip.Checkmate on a whole resident clip: frames[f] / dsts[f] are the device planes of frame f. One vszip_checkmate over
         all planes of the clip; a frame's neighbours are the clip's other frames (nothing is copied)."""
         self.prepared_checkmate_clip(frames, dsts, thr, tmax, tthr2)()
+
+    def _mosquito_args(self, srcs, dsts, strength, restore, radius, bits, chroma):
+        n = len(srcs)
+        per = lambda v: [int(v)] * n if isinstance(v, (int, np.integer)) else [int(x) for x in v]
+        st, rs, rd = per(strength), per(restore), per(radius)
+        if not (len(st) == len(rs) == len(rd) == n):
+            raise ValueError("mosquito_nr: strength, restore and radius are scalars or one value per plane")
+        dt = srcs[0].dtype
+        b = int(bits) if bits is not None else 8 * dt.itemsize
+        i32 = lambda v: (C.c_int32 * n)(*v)
+        ch = None
+        if chroma is not None:
+            ch = (C.c_uint8 * n)(*([int(bool(chroma))] * n if isinstance(chroma, (bool, int, np.integer)) else [int(bool(c)) for c in chroma]))
+        return (_NP2DT[dt], b, self.plane_table(srcs, dsts), n, i32(st), i32(rs), i32(rd), ch)
+
+    def mosquito_nr(self, srcs, dsts, strength=16, restore=128, radius=2, bits=None, chroma=None):
+        """vszip.MosquitoNR on every plane of srcs (u8, u16 with `bits` 9 .. 16, or f32; any sizes from 4 x 4): strength, restore and
+        radius are scalars or one value per plane; chroma (float planes: the clamp is [-0.5, 0.5]) likewise, None = all luma. Planes
+        with strength 0 are copied. dsts must not overlap srcs."""
+        self.check(self.lib.vszip_mosquito_nr(self.ctx, *self._mosquito_args(srcs, dsts, strength, restore, radius, bits, chroma)))
+
+    def prepared_mosquito_nr(self, srcs, dsts, strength=16, restore=128, radius=2, bits=None, chroma=None):
+        """-> a callable queueing vszip_mosquito_nr on argument blocks built once."""
+        fn, ctx, check, args = self.lib.vszip_mosquito_nr, self.ctx, self.check, self._mosquito_args(srcs, dsts, strength, restore, radius, bits, chroma)
+        return lambda: check(fn(ctx, *args))
 
     def prepared_limit_filter(self, flts, srcs, dsts, dark_thr, bright_thr, elast):
         """-> a callable queueing vszip_limit_filter (no third clip) on argument blocks built once."""
