@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define VSZIP_ABI_VERSION 4 /* additive since 4: vszip_clahe, vszip_comb_mask, vszip_comb_mask_mt, vszip_checkmate, vszip_mosquito_nr; 4 (round 5): vszip_dev_alloc searches a bounded number of candidates and keeps nothing (below); vszip_dev_arena_info added; vszip_dev_trim, vszip_dev_placement_info and
+#define VSZIP_ABI_VERSION 4 /* additive since 4: vszip_clahe, vszip_comb_mask, vszip_comb_mask_mt, vszip_checkmate, vszip_mosquito_nr, vszip_deband, vszip_deband_tables; 4 (round 5): vszip_dev_alloc searches a bounded number of candidates and keeps nothing (below); vszip_dev_arena_info added; vszip_dev_trim, vszip_dev_placement_info and
                                vszip_dev_alloc_probed removed (nothing is searched for or parked any more); 3 (round 4): vszip_ctx_set_option / _get_option, vszip_dev_probe_region,
                                vszip_plane_average_async, vszip_plane_minmax_async added; 2 (round 3): vszip_ssim_source grew (YUV sources); entry points added since 1:
                                vszip_chain_run, vszip_ssimulacra2_src, vszip_to_rgbs_linear, vszip_probe_read_each, vszip_resample_table */
@@ -119,7 +119,7 @@ int vszip_probe_read_each(vszip_ctx *ctx, double *total_ms, int *launches, float
  * Plane memory: what a call reads and writes. Valid for every entry point that takes planes: the vszip_plane table calls
  * and the pointer-array calls (vszip_ssimulacra2 / _src, vszip_to_rgbs_linear, vszip_xpsnr_wsse / _batch, the sclips /
  * mclips of vszip_eedi3 / _mclip, vszip_limit_filter's refs, vszip_adaptive_binarize's second clip, vszip_comb_mask's
- * previous frame in `ref` and the neighbouring frames' planes of vszip_checkmate's vszip_temporal_nbrs, which are inputs
+ * previous frame in `ref`, the tables and grain of vszip_deband's vszip_deband_plane and the neighbouring frames' planes of vszip_checkmate's vszip_temporal_nbrs, which are inputs
  * under clauses 1-3 with the size of the entry's plane and pitches of their own: h x stride readable each). A plane is
  * (pointer, stride, w, h) with stride >= w. Derived from the kernels ("Furthest read of every
  * kernel") and kept by tests/test_gpu_footprint.py.
@@ -155,7 +155,12 @@ int vszip_probe_read_each(vszip_ctx *ctx, double *total_ms, int *launches, float
  *    library does not). vszip_mosquito_nr reads a 9 x 9 neighbourhood: clauses 1-4 hold, its dst must not overlap src (for a
  *    plane with strength 0, which is copied, too), bases and pitches that are not multiples of four samples take a slower
  *    path with the same bits, and integer samples above 2^bits - 1 are not an error: they are processed as the reference
- *    would process them and the result is clamped to 2^bits - 1. Partial overlap is never allowed.
+ *    would process them and the result is clamped to 2^bits - 1. vszip_deband reads two or four samples at per-sample offsets of up to
+ *    128 samples in both directions, always inside [0, w) x h (every sampled coordinate is clamped, whatever the table holds): clauses 1-4 hold,
+ *    its dst must not overlap src, only [0, w) x h of dst is written, and bases and pitches that are not multiples of four samples take a
+ *    slower path with the same bits. Its offset tables and grain planes (vszip_deband_plane) are inputs under clauses 1-3 with the size of
+ *    the entry's plane and pitches of their own: h x offsets_pitch pairs and h x grain_pitch samples readable each; no output depends on their
+ *    padding either. Partial overlap is never allowed.
  */
 typedef struct vszip_plane {
     const void *src; /* input plane */
@@ -303,6 +308,82 @@ int vszip_checkmate(vszip_ctx *ctx, const vszip_plane *planes, const vszip_tempo
  */
 int vszip_mosquito_nr(vszip_ctx *ctx, int dtype, int bits_per_sample, const vszip_plane *planes, int nplanes,
                       const int32_t *strength, const int32_t *restore, const int32_t *radius, const uint8_t *chroma);
+
+/*
+ * Deband — f3kdb-style debanding with grain: replaces processPlane of src/filters/deband_int.zig:93-340 and
+ * src/filters/deband_float.zig:88-309 (with fillAnglePlane / calculateGradientAngle and the polynomial pow / atan of src/vcl.zig)
+ * as called per plane by F3KDB(...).getFrame, and the create-time tables of TempBuff.initFrameLuts
+ * (src/vapoursynth/deband.zig:162-319, generators :336-431).
+ *
+ * vszip_deband_tables (device-free). Fills caller-provided HOST arrays for one clip geometry; with luma == NULL it only fills
+ * `sizes` (the query). Outputs:
+ *   luma, chroma   int8 pairs (val1, val2), one pair per plane sample, row pitch = the plane's width in pairs (chroma:
+ *                  sizes.chroma_w x sizes.chroma_h = the luma size divided by 2^ssw x 2^ssh, rounded up); val2 = 0 outside
+ *                  sample mode 2. These are the refEncode()d values themselves (0..127, or -128 where the reference's signed
+ *                  char wraps), not multiplied by any pitch; the chroma entry at (cx, cy) is the luma entry at
+ *                  (cx << ssw, cy << ssh) and the kernel applies the arithmetic >> ssw / >> ssh;
+ *   grain_y/_c     sizes.grain_items values each (((width + 255) & ~127) * height, times 3 for dynamic grain), int16 for
+ *                  integer clips and f32 for float clips; NULL (or strength 0) skips the buffer, its random values are
+ *                  consumed all the same;
+ *   grain_offsets  dynamic grain: one offset into both grain buffers per frame, (items + uniform(items)) & ~15;
+ *   max_offset     the largest |val| in the tables (what vszip_deband wants to know).
+ * grain_u16 / grain_f32 are the strengths on the clip's scale (what Data.scaleValue makes of the 8-bit-scale `grain`).
+ * VSZIP_ERR_ARG with the reference's create-time wording in `err` (may be NULL) for the range checks of Data.setData that
+ * concern these inputs, in its order: sample_mode [1..7], range [0..255], random_param_ref / _grain [0..255],
+ * random_algo_ref / _grain [0..2] ('Deband: parameter "range=256" out of range [0..255].'). The checks of thr, thr1, thr2 and
+ * grain are on the wrapper's 8-bit scale and stay with the host; angle_boost and max_angle are checked by vszip_deband.
+ *
+ * vszip_deband. dtype VSZIP_U16 (samples on the 16-bit scale: the reference always works at 16 bits; the conversion of
+ * clips under 16 bits and the dither back are the host's resizer) or VSZIP_F32. planes[i].src / dst as everywhere (`ref` is
+ * not used); per[i] sits beside planes[i] as vszip_temporal_nbrs does:
+ *   offsets, offsets_pitch  DEVICE pointer to the plane's table (luma or chroma) and its row pitch in pairs;
+ *   ssw, ssh                the shifts to apply to the table's values (0 for luma);
+ *   grain, grain_pitch      DEVICE pointer to the plane's grain (int16 for VSZIP_U16, f32 for VSZIP_F32), already advanced by
+ *                           the frame's grain offset, and the pitch in samples the reference indexes it with (VapourSynth's
+ *                           row pitch of the plane: the width rounded up to 32 bytes for the reference's goldens). It is
+ *                           independent of the pitches of the planes given here. NULL: no grain;
+ *   thr, thr1, thr2         on the clip's scale (integral values for VSZIP_U16); lo, hi: the output clamp.
+ * Any number of planes of any sizes in one call; the planes of many frames share the same table pointers. sample_mode 1..7,
+ * blur_first, angle_boost and max_angle are the wrapper's arguments; max_offset is the largest |val| of the tables used
+ * (0..128). Entries beyond max_offset give an unspecified sample and no out-of-plane access: every sampled coordinate is
+ * clamped, into the plane or into the tile a workgroup staged (for tables from vszip_deband_tables the clamp never changes
+ * a coordinate). Two gather paths: a workgroup stages its tile and a halo of 32 samples in LDS (max_offset <= 32), or
+ * gathers from global memory (any max_offset); VSZIP_DEBAND_PATH (csrc/options.inc) forces one. Sample mode 7 first writes the
+ * normalised gradient angle of every plane into the context's scratch (grow-only; at most VSZIP_DEBAND_SCRATCH_MIB per
+ * plane group, a plane is never split). Bit-exact with the reference in both sample types, float included. Asynchronous on
+ * the context stream. "Plane memory": clauses 1-4 hold; only [0, w) x h of dst is written; dst must not overlap src;
+ * bases and pitches (planes, table, grain) that are not multiples of four samples take a slower path with the same
+ * bits; of a table (grain) plane h x offsets_pitch pairs (h x grain_pitch samples) must be readable. VSZIP_ERR_ARG with the
+ * wrapper's wording for sample_mode, angle_boost [0..65535] and max_angle [0..1]; and for a dtype other than U16 / F32, a
+ * max_offset outside 0..128, a NULL src, dst or table.
+ */
+typedef struct vszip_deband_cfg {
+    int32_t width, height, ssw, ssh, num_frames; /* the clip: luma size, log2 chroma subsampling, frame count */
+    int32_t range, sample_mode;
+    int32_t seed, random_algo_ref, random_algo_grain; /* generators: 0 old, 1 uniform, 2 gaussian */
+    double random_param_ref, random_param_grain;
+    int32_t is_float, dynamic_grain;
+    uint16_t grain_u16[2]; /* integer clips: luma, chroma strength on the 16-bit scale */
+    float grain_f32[2];    /* float clips */
+} vszip_deband_cfg;
+typedef struct vszip_deband_sizes {
+    size_t luma_pairs, chroma_pairs, grain_items, grain_offsets;
+    int32_t chroma_w, chroma_h;
+} vszip_deband_sizes;
+typedef struct vszip_deband_plane {
+    const int8_t *offsets;
+    ptrdiff_t offsets_pitch;
+    const void *grain;
+    ptrdiff_t grain_pitch;
+    int32_t ssw, ssh;
+    float thr, thr1, thr2;
+    float lo, hi;
+} vszip_deband_plane;
+
+int vszip_deband_tables(const vszip_deband_cfg *cfg, vszip_deband_sizes *sizes, int8_t *luma, int8_t *chroma, void *grain_y,
+                        void *grain_c, uint32_t *grain_offsets, int32_t *max_offset, char *err, size_t err_cap);
+int vszip_deband(vszip_ctx *ctx, int dtype, const vszip_plane *planes, const vszip_deband_plane *per, int nplanes,
+                 int sample_mode, int blur_first, float angle_boost, float max_angle, int max_offset);
 
 /*
  * PlaneMinMax — replaces filter.minMax / minMaxRef / minMaxNoThr / minMaxNoThrRef

@@ -45,6 +45,26 @@ class TemporalNbrs(C.Structure):
     ]
 
 
+class DebandCfg(C.Structure):
+    """vszip_deband_cfg"""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("ssw", C.c_int32), ("ssh", C.c_int32), ("num_frames", C.c_int32), ("range", C.c_int32),
+                ("sample_mode", C.c_int32), ("seed", C.c_int32), ("random_algo_ref", C.c_int32), ("random_algo_grain", C.c_int32),
+                ("random_param_ref", C.c_double), ("random_param_grain", C.c_double), ("is_float", C.c_int32), ("dynamic_grain", C.c_int32),
+                ("grain_u16", C.c_uint16 * 2), ("grain_f32", C.c_float * 2)]
+
+
+class DebandSizes(C.Structure):
+    """vszip_deband_sizes"""
+    _fields_ = [("luma_pairs", C.c_size_t), ("chroma_pairs", C.c_size_t), ("grain_items", C.c_size_t), ("grain_offsets", C.c_size_t),
+                ("chroma_w", C.c_int32), ("chroma_h", C.c_int32)]
+
+
+class DebandPlane(C.Structure):
+    """vszip_deband_plane"""
+    _fields_ = [("offsets", C.c_void_p), ("offsets_pitch", C.c_ssize_t), ("grain", C.c_void_p), ("grain_pitch", C.c_ssize_t), ("ssw", C.c_int32), ("ssh", C.c_int32),
+                ("thr", C.c_float), ("thr1", C.c_float), ("thr2", C.c_float), ("lo", C.c_float), ("hi", C.c_float)]
+
+
 class BilateralCfg(C.Structure):
     _fields_ = [
         ("sigmaS", C.c_double), ("sigmaR", C.c_double), ("process", C.c_int32), ("algorithm", C.c_int32),
@@ -132,6 +152,8 @@ SYMBOLS = {
     "vszip_comb_mask_mt": (_i, [_vp, _PP, _i, _i, _i]),
     "vszip_checkmate": (_i, [_vp, _PP, C.POINTER(TemporalNbrs), _i, _i, _i, _i]),
     "vszip_mosquito_nr": (_i, [_vp, _i, _i, _PP, _i, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_uint8)]),
+    "vszip_deband_tables": (_i, [C.POINTER(DebandCfg), C.POINTER(DebandSizes), _vp, _vp, _vp, _vp, _vp, C.POINTER(C.c_int32), C.c_char_p, _sz]),
+    "vszip_deband": (_i, [_vp, _i, _PP, C.POINTER(DebandPlane), _i, _i, _i, C.c_float, C.c_float, _i]),
     "vszip_plane_average": (_i, [_vp, _i, _PP, _i, C.POINTER(C.c_int32), _i, _i, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "vszip_plane_minmax": (_i, [_vp, _i, _PP, _i, C.c_float, C.c_float, _i, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "vszip_plane_average_async": (_i, [_vp, _i, _PP, _i, C.POINTER(C.c_int32), _i, _i, _vp]),
@@ -149,6 +171,37 @@ def resample_table(src_dim: int, dst_dim: int, shift: float = 0.0):
     if rc != 0:
         raise ValueError(f"vszip_resample_table({src_dim}, {dst_dim}, {shift}) -> {rc}")
     return left, coef
+
+
+def deband_tables(width, height, ssw=0, ssh=0, num_frames=1, range=15, sample_mode=2, seed=0, random_algo_ref=1, random_algo_grain=1, random_param_ref=1.0,
+                  random_param_grain=1.0, grain=(0, 0), dynamic_grain=False, is_float=False) -> dict:
+    """vszip_deband_tables (device-free): the per-clip tables of vszip.Deband as numpy arrays. grain: the luma and chroma strengths on the
+    clip's scale (16-bit integers, or f32). -> luma (h, w, 2) int8, chroma (ch, cw, 2) int8, grain_y / grain_c (int16 | f32, None for
+    strength 0), grain_offsets (uint32 per frame, None for static grain), max_offset, items (grain values of one frame).
+    ValueError with the reference's wording for an argument out of range."""
+    cfg = DebandCfg(int(width), int(height), int(ssw), int(ssh), int(num_frames), int(range), int(sample_mode), C.c_int32(int(seed) & 0xFFFFFFFF).value,
+                    int(random_algo_ref), int(random_algo_grain), float(random_param_ref), float(random_param_grain), int(bool(is_float)), int(bool(dynamic_grain)))
+    for i in (0, 1):
+        if is_float:
+            cfg.grain_f32[i] = float(grain[i])
+        else:
+            cfg.grain_u16[i] = int(grain[i])
+    lib, sizes, err = load(), DebandSizes(), C.create_string_buffer(256)
+    rc = lib.vszip_deband_tables(C.byref(cfg), C.byref(sizes), None, None, None, None, None, None, err, len(err))
+    if rc != 0:
+        raise ValueError(err.value.decode() or f"vszip_deband_tables -> {rc}")
+    luma = np.empty((int(height), int(width), 2), np.int8)
+    chroma = np.empty((sizes.chroma_h, sizes.chroma_w, 2), np.int8)
+    gt = np.float32 if is_float else np.int16
+    gy = np.empty(sizes.grain_items, gt) if grain[0] > 0 else None
+    gc = np.empty(sizes.grain_items, gt) if grain[1] > 0 else None
+    offs = np.empty(sizes.grain_offsets, np.uint32) if sizes.grain_offsets else None
+    mx = C.c_int32()
+    ptr = lambda a: a.ctypes.data if a is not None else None
+    rc = lib.vszip_deband_tables(C.byref(cfg), C.byref(sizes), ptr(luma), ptr(chroma), ptr(gy), ptr(gc), ptr(offs), C.byref(mx), err, len(err))
+    if rc != 0:
+        raise ValueError(err.value.decode() or f"vszip_deband_tables -> {rc}")
+    return dict(luma=luma, chroma=chroma, grain_y=gy, grain_c=gc, grain_offsets=offs, max_offset=mx.value, items=sizes.grain_items // (3 if dynamic_grain else 1))
 
 
 def _share_torch_hip_runtime():
@@ -565,6 +618,39 @@ class Device:
     def prepared_mosquito_nr(self, srcs, dsts, strength=16, restore=128, radius=2, bits=None, chroma=None):
         """-> a callable queueing vszip_mosquito_nr on argument blocks built once."""
         fn, ctx, check, args = self.lib.vszip_mosquito_nr, self.ctx, self.check, self._mosquito_args(srcs, dsts, strength, restore, radius, bits, chroma)
+        return lambda: check(fn(ctx, *args))
+
+    def upload_deband_tables(self, tab: dict) -> dict:
+        """The tables of deband_tables() (or of the numpy spec) resident on the device, uploaded once per clip: `luma` / `chroma` as
+        DevPlanes of int16 (one pair a sample), `grain_y` / `grain_c` as one-row DevPlanes or None; the host-side entries are kept."""
+        dev = dict(tab)
+        for k in ("luma", "chroma"):
+            dev[k] = self.upload(np.ascontiguousarray(tab[k]).view(np.int16).reshape(tab[k].shape[0], tab[k].shape[1]))
+        for k in ("grain_y", "grain_c"):
+            dev[k] = self.upload(tab[k].reshape(1, -1)) if tab[k] is not None else None
+        return dev
+
+    def deband_entry(self, table, ssw=0, ssh=0, grain=None, grain_offset=0, grain_pitch=0, thr=0, thr1=None, thr2=None, lo=0, hi=65535) -> DebandPlane:
+        """one vszip_deband_plane: `table` / `grain` are DevPlanes of upload_deband_tables (or any device memory wrapped alike)"""
+        g = grain.ptr + int(grain_offset) * grain.dtype.itemsize if grain is not None else None
+        return DebandPlane(table.ptr, table.stride, g, int(grain_pitch), int(ssw), int(ssh), float(thr), float(thr if thr1 is None else thr1),
+                           float(thr if thr2 is None else thr2), float(lo), float(hi))
+
+    def _deband_args(self, srcs, dsts, entries, sample_mode, blur_first, angle_boost, max_angle, max_offset):
+        n = len(srcs)
+        if len(entries) != n or len(dsts) != n:
+            raise ValueError("deband: one destination and one vszip_deband_plane entry per plane")
+        return (_NP2DT[srcs[0].dtype], self.plane_table(srcs, dsts), (DebandPlane * n)(*entries), n, int(sample_mode), int(bool(blur_first)), float(angle_boost),
+                float(max_angle), int(max_offset))
+
+    def deband(self, srcs, dsts, entries, sample_mode=2, blur_first=True, angle_boost=1.5, max_angle=0.15, max_offset=128):
+        """vszip.Deband on every plane of srcs (u16 on the 16-bit scale, or f32; any sizes): entries[i] (deband_entry) names plane i's offset
+        table, grain, thresholds and clamp; max_offset is the largest |value| of the tables used. dsts must not overlap srcs."""
+        self.check(self.lib.vszip_deband(self.ctx, *self._deband_args(srcs, dsts, entries, sample_mode, blur_first, angle_boost, max_angle, max_offset)))
+
+    def prepared_deband(self, srcs, dsts, entries, sample_mode=2, blur_first=True, angle_boost=1.5, max_angle=0.15, max_offset=128):
+        """-> a callable queueing vszip_deband on argument blocks built once."""
+        fn, ctx, check, args = self.lib.vszip_deband, self.ctx, self.check, self._deband_args(srcs, dsts, entries, sample_mode, blur_first, angle_boost, max_angle, max_offset)
         return lambda: check(fn(ctx, *args))
 
     def prepared_limit_filter(self, flts, srcs, dsts, dark_thr, bright_thr, elast):

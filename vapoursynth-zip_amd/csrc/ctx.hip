@@ -87,6 +87,7 @@ const OptionRange kRanges[] = {
     {"VSZIP_RT_VSMALL_MAX", 0, 8},     {"VSZIP_RT_VBAND", 0, 1 << 16},           {"VSZIP_RT_VRING_MAXR", 0, 127},   {"VSZIP_RT_GROUP_MB", 0, 1 << 20},
     {"VSZIP_RING_PERIODS", 0, 1 << 16},
     {"VSZIP_CLAHE_SCRATCH_MIB", 1, 1 << 20},
+    {"VSZIP_DEBAND_SCRATCH_MIB", 1, 1 << 20}, {"VSZIP_DEBAND_PATH", 0, 2},
 };
 bool option_in_range(const char *env, int v) {
     for (const OptionRange &r : kRanges)

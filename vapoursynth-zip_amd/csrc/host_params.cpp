@@ -4,6 +4,9 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
 #include <vector>
 
 #include "../../include/vszip_hip.h"
@@ -149,6 +152,173 @@ VSZIP_EXPORT int vszip_resample_table(int src_dim, int dst_dim, double shift, in
         const int l = std::min(first, src_dim - width);
         left[i] = l;
         for (int k = 0; k < kTaps; ++k) coef4[4 * i + k] = (l + k < src_dim) ? (float)row[(size_t)(l + k)] : 0.0f;
+    }
+    return VSZIP_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// Deband: the create-time tables of TempBuff.initFrameLuts (src/vapoursynth/deband.zig:162-319) with the generators of
+// :336-431. One 32-bit state, mixed from seed, width, height and the frame count, serves everything in one serial
+// order: per luma sample a grain dummy, one offset (two in mode 2) where the sample is at least one sample from the
+// edges the mode looks at, and two grain dummies at every chroma site; then the luma and the chroma grain buffers (a
+// plane without grain still consumes its values); then, for dynamic grain, one uniform value per frame. The tables hold
+// the refEncode()d values themselves, not multiplied by a pitch: vszip_deband reads src[y +- dy][x +- dx].
+// ---------------------------------------------------------------------------------------------------------
+namespace {
+struct DebandRng {
+    uint32_t s;
+    static double to_double(uint32_t v) {  // randToDouble: the state as the mantissa of a double in [1, 2), mapped to [-1, 1)
+        uint64_t raw = ((uint64_t)v << 20) | ((uint64_t)v >> 12);
+        raw |= 0x3ff0000000000000ull;
+        double d;
+        std::memcpy(&d, &raw, sizeof d);
+        return (d - 1.0) * 2.0 - 1.0;
+    }
+    double old() {
+        const uint32_t t = (((s << 13) ^ s) >> 17) ^ (s << 13) ^ s;
+        s = (32u * t) ^ t;
+        return to_double(s);
+    }
+    double uniform() {
+        s = 1664525u * s + 1013904223u;
+        return to_double(s);
+    }
+    double gaussian(double param) {
+        for (;;) {
+            double x, y, r2;
+            do {
+                x = uniform();
+                y = uniform();
+                r2 = x * x + y * y;
+            } while (!(r2 <= 1.0 && r2 != 0.0));
+            const double v = param * y * std::sqrt(-2.0 * std::log(r2) / r2);
+            if (v > -1.0 && v < 1.0) return v;
+        }
+    }
+    double real(int algo, double param) { return algo == 0 ? old() : (algo == 1 ? uniform() : gaussian(param)); }
+    int32_t value(int algo, int32_t range, double param) { return (int32_t)std::round(real(algo, param) * (double)range); }
+};
+
+int deband_ref_encode(int32_t r) {  // neo_f3kdb's signed char: truncate, abs, truncate again: 128 comes back as -128
+    const int t = (int8_t)(uint8_t)(uint32_t)r;
+    const int a = t < 0 ? -t : t;
+    return (int8_t)(uint8_t)a;
+}
+
+// Zig's {d}: integers without a point, other values in the shortest decimal form that reads back as the same double
+void deband_fmt(char *out, size_t cap, double v) {
+    if (v == std::floor(v) && std::fabs(v) < 1e15) {
+        std::snprintf(out, cap, "%.0f", v);
+        return;
+    }
+    for (int p = 1; p <= 17; ++p) {
+        std::snprintf(out, cap, "%.*f", p, v);
+        if (std::strtod(out, nullptr) == v) return;
+    }
+}
+
+int deband_range_error(char *err, size_t cap, const char *key, double v, double lo, double hi) {
+    if (err && cap) {
+        char a[64], b[64], c[64];
+        deband_fmt(a, sizeof a, v);
+        deband_fmt(b, sizeof b, lo);
+        deband_fmt(c, sizeof c, hi);
+        std::snprintf(err, cap, "Deband: parameter \"%s=%s\" out of range [%s..%s].", key, a, b, c);
+    }
+    return VSZIP_ERR_ARG;
+}
+}  // namespace
+
+VSZIP_EXPORT int vszip_deband_tables(const vszip_deband_cfg *cfg, vszip_deband_sizes *sizes, int8_t *luma, int8_t *chroma, void *grain_y, void *grain_c,
+                                     uint32_t *grain_offsets, int32_t *max_offset, char *err, size_t err_cap) {
+    if (err && err_cap) err[0] = 0;
+    if (!cfg) return VSZIP_ERR_ARG;
+    // Data.setData's range checks on what this function is given, in its order and wording
+    struct Check {
+        const char *key;
+        double v, lo, hi;
+    } const checks[] = {
+        {"sample_mode", (double)cfg->sample_mode, 1, 7},
+        {"range", (double)cfg->range, 0, 255},
+        {"random_param_ref", cfg->random_param_ref, 0, 255},
+        {"random_param_grain", cfg->random_param_grain, 0, 255},
+        {"random_algo_ref", (double)cfg->random_algo_ref, 0, 2},
+        {"random_algo_grain", (double)cfg->random_algo_grain, 0, 2},
+    };
+    for (const Check &c : checks)
+        if (!(c.v >= c.lo && c.v <= c.hi)) return deband_range_error(err, err_cap, c.key, c.v, c.lo, c.hi);
+    const int w = cfg->width, h = cfg->height, ssw = cfg->ssw, ssh = cfg->ssh, mode = cfg->sample_mode;
+    if (w <= 0 || h <= 0 || ssw < 0 || ssw > 4 || ssh < 0 || ssh > 4 || cfg->num_frames <= 0 || (int64_t)w * h > (int64_t)1 << 28) {
+        if (err && err_cap) std::snprintf(err, err_cap, "Deband: bad geometry %dx%d, subsampling %d/%d, %d frames", w, h, ssw, ssh, cfg->num_frames);
+        return VSZIP_ERR_ARG;
+    }
+    const bool dynamic = cfg->dynamic_grain != 0;
+    const int cw = (w + (1 << ssw) - 1) >> ssw, ch = (h + (1 << ssh) - 1) >> ssh;
+    const size_t items = (size_t)(((uint32_t)w + 255u) & 0xffffff80u) * (size_t)h, total = items * (dynamic ? 3 : 1);
+    if (sizes) {
+        sizes->luma_pairs = (size_t)w * h;
+        sizes->chroma_pairs = (size_t)cw * ch;
+        sizes->grain_items = total;
+        sizes->grain_offsets = dynamic ? (size_t)cfg->num_frames : 0;
+        sizes->chroma_w = cw;
+        sizes->chroma_h = ch;
+    }
+    if (!luma) return VSZIP_OK;  // the query
+    if (!chroma || (dynamic && !grain_offsets)) return VSZIP_ERR_ARG;
+
+    const uint32_t w32 = (uint32_t)w, h32 = (uint32_t)h, nf32 = (uint32_t)cfg->num_frames;
+    DebandRng r;
+    r.s = 0x92D68CA2u - (uint32_t)cfg->seed;
+    r.s ^= (w32 << 16) ^ h32;
+    r.s ^= (nf32 << 16) ^ nf32;
+    const int ar = cfg->random_algo_ref, ag = cfg->random_algo_grain, mask_w = (1 << ssw) - 1, mask_h = (1 << ssh) - 1;
+    const double pr = cfg->random_param_ref, pg = cfg->random_param_grain;
+    int largest = 0;
+    for (int y = 0; y < h; ++y) {
+        const int y_range = std::min(std::min(cfg->range, y), h - y - 1);
+        int cx = 0;
+        for (int x = 0; x < w; ++x) {
+            (void)r.real(ag, pg);
+            const int x_range = std::min(std::min(cfg->range, x), w - x - 1);
+            const int cur = mode == 1 ? y_range : (mode == 3 ? x_range : std::min(x_range, y_range));
+            int v1 = 0, v2 = 0;
+            if (cur > 0) {
+                v1 = deband_ref_encode(r.value(ar, cur, pr));
+                if (mode == 2) v2 = deband_ref_encode(r.value(ar, cur, pr));
+            }
+            int8_t *l = luma + 2 * ((size_t)y * w + x);
+            l[0] = (int8_t)v1;
+            l[1] = (int8_t)v2;
+            largest = std::max(largest, std::max(std::abs(v1), std::abs(v2)));
+            if ((x & mask_w) == 0 && (y & mask_h) == 0) {
+                int8_t *c = chroma + 2 * ((size_t)(y >> ssh) * cw + cx);
+                c[0] = (int8_t)v1;
+                c[1] = (int8_t)v2;
+                (void)r.real(ag, pg);
+                (void)r.real(ag, pg);
+                ++cx;
+            }
+        }
+    }
+    if (max_offset) *max_offset = largest;
+    void *const bufs[2] = {grain_y, grain_c};
+    for (int i = 0; i < 2; ++i) {
+        const bool on = cfg->is_float ? cfg->grain_f32[i] > 0.0f : cfg->grain_u16[i] > 0;
+        if (!on || !bufs[i]) {
+            for (size_t k = 0; k < total; ++k) (void)r.real(ag, pg);
+        } else if (cfg->is_float) {
+            float *g = static_cast<float *>(bufs[i]);
+            const double range = (double)cfg->grain_f32[i];
+            for (size_t k = 0; k < total; ++k) g[k] = (float)(r.real(ag, pg) * range);
+        } else {
+            int16_t *g = static_cast<int16_t *>(bufs[i]);
+            const int32_t range = cfg->grain_u16[i];
+            for (size_t k = 0; k < total; ++k) g[k] = (int16_t)r.value(ag, range, pg);
+        }
+    }
+    if (dynamic) {
+        const int32_t ic = (int32_t)items;
+        for (int f = 0; f < cfg->num_frames; ++f) grain_offsets[f] = (uint32_t)(ic + r.value(1, ic, 1.0)) & 0xfffffff0u;
     }
     return VSZIP_OK;
 }
