@@ -34,7 +34,10 @@
 //     from plane columns 0..r (two 1-pixel loads per step), which frees two
 //     lanes and makes 480 output columns per wave (3840 = 8 tiles, 1920 = 4,
 //     960 = 2); blockIdx is remapped so that neighbouring tiles/bands run on
-//     one XCD and find their halo in that XCD's L2.
+//     one XCD and find their halo in that XCD's L2. 16-bit planes up to
+//     r = 13 take rows and K columns through a small queue in LDS instead
+//     (RingGeom::QD): loads that write LDS directly, one hand-counted wait a
+//     step, no 1-pixel loads.
 //   boxblur_ct_int_kernel   (any alignment / stride): window rows re-read from
 //     cache, first lanes own columns [0, r] for E_0.
 #pragma once
@@ -340,7 +343,60 @@ __global__ __launch_bounds__(64) void boxblur_ct_int_kernel(const BBParams prm) 
 // ---------------------------------------------------------------------------
 
 // RV: the vertical radius — R, or 0 for a horizontal-only blur (round 4: the window is then the row itself, the ring only its prefetch)
-template <int R, int SLOT_VGPRS = 4, int PXN = 8, int RV = R>
+// Rows queued in LDS ahead of the register ring (0: none, rows are loaded into the ring's own landing slots). The queued form is the fast 16-byte-a-lane
+// form of 16-bit planes, see RingGeom::QD. Measured on 64 4K YUV420P16 frames against the register-only form, both in one process, on three devices
+// (profiles/ring_prefetch.md): depth 2 takes 2 % off r = 13, 1.6 % off r = 9 and 11 and 5 % off r = 2 and 5; depths 3 ... 7 give that back (r = 13: 552 us at 2,
+// 570 at 4 and 7, 564 without the queue), so the depth of the prefetch is not what limits this kernel. What depth 2 wins is a step of three vector-memory
+// instructions instead of four and 5 % fewer bytes read. From r = 14 on (two waves a SIMD, rows 3-7 deep in registers) depth 2 loses 10 % and stays off;
+// depth 6 (-DVSZIP_RING_QD_HI=6) lost 2 % at r = 14 and won 2 % at r = 20 on the one device it ran on.
+#ifndef VSZIP_RING_QD
+#define VSZIP_RING_QD 2
+#endif
+#ifndef VSZIP_RING_QD_HI  // (radii above kRingQueueMaxR)
+#define VSZIP_RING_QD_HI 0
+#endif
+constexpr int kRingQueueMaxR = 13;
+template <int R, int SLOT_VGPRS, int PXN, int RV, int QDEPTH>
+struct RingGeom;
+// the deepest queue up to VSZIP_RING_QD rows that costs this radius no workgroup a CU (RingGeom::FITS)
+template <int R, int Q>
+constexpr int ring_queue_fit() {
+    if constexpr (Q < 2)
+        return 0;
+    else if constexpr (RingGeom<R, 4, 8, R, Q>::FITS)
+        return Q;
+    else
+        return ring_queue_fit<R, Q - 1>();
+}
+template <typename T, int R>
+constexpr int ring_queue_depth() {
+    if constexpr (sizeof(T) == 2)
+        return ring_queue_fit<R, (R <= kRingQueueMaxR ? VSZIP_RING_QD : VSZIP_RING_QD_HI)>();
+    else
+        return 0;
+}
+
+// 16 bytes a lane from a buffer straight into LDS (lane l lands at lds_byte + 16 l). The load holds no VGPR while it is in flight, and hipcc does not know of
+// it: it never waits for it, so every wait is written by hand (RingWave::step). M0 carries the LDS address and is written in the statement that uses it.
+__device__ __forceinline__ void ring_dma16(__amdgpu_buffer_rsrc_t rs, uint32_t lds_byte, uint32_t voff, uint32_t soff) {
+    uint32_t keep;
+    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tbuffer_load_dwordx4 %2, %3, %4 offen lds\n\ts_mov_b32 m0, %0"
+                 : "=&s"(keep)
+                 : "s"(lds_byte), "v"(voff), "s"(rs), "s"(soff)
+                 : "memory");
+}
+// the same with only the first LANES lanes switched on (a lane that is merely out of range would still write its 16 zero bytes)
+template <int LANES>
+__device__ __forceinline__ void ring_dma16_first(__amdgpu_buffer_rsrc_t rs, uint32_t lds_byte, uint32_t voff, uint32_t soff) {
+    uint32_t keep;
+    uint64_t keep_exec;
+    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b64 %1, exec\n\ts_mov_b32 m0, %2\n\ts_mov_b64 exec, %6\n\tbuffer_load_dwordx4 %3, %4, %5 offen lds\n\ts_mov_b64 exec, %1\n\ts_mov_b32 m0, %0"
+                 : "=&s"(keep), "=&s"(keep_exec)
+                 : "s"(lds_byte), "v"(voff), "s"(rs), "s"(soff), "n"((1 << LANES) - 1)
+                 : "memory");
+}
+
+template <int R, int SLOT_VGPRS, int PXN, int RV, int QDEPTH>
 struct RingGeom {
     static constexpr int K = 2 * RV + 1;  // rows of the (vertical) window
     static constexpr int HL = ((R + 1 + PXN - 1) / PXN) * PXN;  // left halo  (>= R + 1)
@@ -357,17 +413,29 @@ struct RingGeom {
     // VGPRs a SIMD lane has). A shallow prefetch (D = 1) is taken when it buys a wave per SIMD —
     // the other waves then hide the latency; otherwise D is 3, 5 or 7, whichever makes NR a
     // multiple of KL, the prefetch ring of the K_row column pixels (statically indexed, S % KL).
+    // With a row queue (QD > 0, below) D is 1 and the depth is the queue's.
     static constexpr int est_vgprs(int d) { return (2 * RV + 1 + d) * SLOT_VGPRS + (PXN == 16 ? 104 : 56); }
     static constexpr int tier(int v) { return v <= 128 ? 4 : (v <= 168 ? 3 : 2); }
     static constexpr int D3 = (2 * RV + 4) % 3 == 0 ? 3 : ((2 * RV + 6) % 3 == 0 ? 5 : 7);
+    // QD > 0: the prefetch depth comes from LDS instead. QD rows of 1 KiB (64 lanes x 16 bytes, as an LDS-DMA writes them) sit between memory and the ring,
+    // which keeps the window and ONE landing slot (D = 1, NR = 2r + 2); a row is requested QD - 1 steps before the step that moves it into the ring, and
+    // holds no register on the way. The K columns come the same way: bytes [0, KB) of every row into a ring of KQ entries that holds the rows from the
+    // leaving one to the newest request.
+    static constexpr int QD = QDEPTH;
+    static_assert(QD == 0 || QD >= 2, "the row queue is read one step after it is refilled");
+    static constexpr int KB = ((R + 1) * (16 / PXN) + 15) / 16 * 16;  // bytes of plane columns 0..r, in whole lanes
+    static constexpr int KQ = 2 * RV + 2 + QD;
 #ifdef VSZIP_RING_D
-    static constexpr int D = VSZIP_RING_D | 1;
+    static constexpr int D = QD > 0 ? 1 : (VSZIP_RING_D | 1);
     static constexpr int KL = (2 * RV + 1 + D) % 3 == 0 ? 3 : 2;
 #else
-    static constexpr bool SHALLOW = tier(est_vgprs(1)) > tier(est_vgprs(D3));
+    static constexpr bool SHALLOW = QD > 0 || tier(est_vgprs(1)) > tier(est_vgprs(D3));
     static constexpr int D = SHALLOW ? 1 : D3;
     static constexpr int KL = SHALLOW ? 2 : 3;
 #endif
+    static constexpr int AHEAD = QD > 0 ? QD : D;  // rows between the newest request and the row entering the window
+    static constexpr int HALO_ROWS = QD > 0 ? 2 * RV : 2 * RV + D;  // rows a band reads that its neighbours read too (the queue stops at the band's last row)
+    static constexpr int LDS_BYTES = 2 * 64 * PXN * 4 + (QD > 0 ? QD * 1024 + KQ * KB : 0);
     static constexpr int NR = 2 * RV + 1 + D;   // ring slots
 #ifdef VSZIP_RING_WPE
     static constexpr int WPE = VSZIP_RING_WPE;
@@ -378,6 +446,8 @@ struct RingGeom {
     static constexpr int WPE = (SLOT_VGPRS == 2 && PXN == 8) ? (tier(est_vgprs(D)) > 3 ? 3 : tier(est_vgprs(D))) : tier(est_vgprs(D));
 #endif
     static_assert(NR % KL == 0, "K-column ring must divide the period");
+    // the queue must not cost a wave: LDS is handed out in blocks of 1 280 bytes, 160 KiB a CU, to 4 * WPE single-wave workgroups
+    static constexpr bool FITS = 4 * WPE * ((LDS_BYTES + 1279) / 1280 * 1280) <= 160 * 1024;
     static constexpr uint32_t MAGIC = K > 1 ? (uint32_t)(((1ull << 32) + K - 1) / K) : 0u;  // ceil(2^32 / k): mulhi(n, MAGIC) == n / k (k = 1: no division)
 };
 
@@ -398,7 +468,9 @@ template <typename T, int R, bool GENERAL, int PXN = 8, bool HONLY = false>
 struct RingWave {
     static_assert(PXN == 8 || (PXN == 16 && sizeof(T) == 1 && !GENERAL), "16 pixels a lane: 8-bit planes, whole 16-pixel groups");
     static constexpr int RV = HONLY ? 0 : R;  // vertical radius
-    using G = RingGeom<R, (int)(sizeof(T) * PXN / 4), PXN, RV>;
+    static constexpr int QD = (!GENERAL && !HONLY && sizeof(T) * PXN == 16) ? ring_queue_depth<T, R>() : 0;
+    using G = RingGeom<R, (int)(sizeof(T) * PXN / 4), PXN, RV, QD>;
+    static_assert(QD == 0 || G::FITS, "row queue too deep for this many workgroups a CU");
     using RawT = RawN<T, PXN>;
     using Vec = decltype(RawT{}.q);
     static constexpr int NR = G::NR;
@@ -436,6 +508,11 @@ struct RingWave {
     __amdgpu_buffer_rsrc_t rs, rd;
     uint32_t sdoff;  // store voffset: doff for output lanes, kOOB for halo lanes
     uint32_t psel;   // v_perm selector: identity, or "reversed half of the mirror partner" (mirrored lanes)
+    // row queue (QD > 0): wave-uniform slot / entry numbers of this step's requests and K reads, LDS byte addresses, the band's end
+    uint32_t q_slot, k_new, k_in, k_out;
+    uint32_t q_lds, k_lds;
+    uint32_t kdoff;  // voffset of the K request: 16 * lane
+    int yend;
     static constexpr uint32_t kOOB = 0xfffffff0u;
 
     __device__ __forceinline__ RawT fetch_off(uint32_t row_off) const {
@@ -649,6 +726,23 @@ struct RingWave {
         // comes with it collapses the D-row prefetch distance to about one row.
         __builtin_amdgcn_sched_barrier(0);
 
+        uint32_t k_enter = 0, k_leave = 0;
+        if constexpr (QD > 0) {
+            // The one wait of a step. A step issues three vector-memory instructions, in this order: the row request, the K request, the store. The row
+            // that this step moves into the ring (i + r + 2) was requested QD - 1 steps ago as the first of its step, so 2 + 3 (QD - 2) younger ones may
+            // stay in flight; the K entries read here are older still. lgkmcnt(0) retires the previous step's LDS reads, and with them the queue slot and
+            // the K entry that the two requests below overwrite. The band's prologue ends on vmcnt(0), so the count holds from the first step.
+            asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(3 * QD - 4) : "memory");
+            __builtin_amdgcn_wave_barrier();
+            // request row i + 1 + r + QD (next_off) and its K columns; past the band's last row the requests go out of range and fetch nothing
+            const bool wanted = i + QD + 2 <= yend;
+            ring_dma16(rs, q_lds + q_slot * 1024u, wanted ? coff : kOOB, next_off);
+            ring_dma16_first<G::KB / 16>(rs, k_lds + k_new * (uint32_t)G::KB, wanted ? kdoff : kOOB, next_off);
+            const T *kq = reinterpret_cast<const T *>(P + 2 * 64 * PXN + QD * 256);
+            k_enter = kq[k_in * (G::KB / sizeof(T)) + kvo / sizeof(T)];
+            k_leave = kq[k_out * (G::KB / sizeof(T)) + kvo / sizeof(T)];
+        }
+
         // B (first half): LDS reads of the previous row's prefix. The very first step of a
         // band has no previous row: it reads stale LDS and its store is switched off.
         uint32_t e[PXN];
@@ -705,17 +799,28 @@ struct RingWave {
             unpackN(ring[S], sb);
 #pragma unroll
             for (int k = 0; k < PXN; ++k) col[k] += a[k] - sb[k];
+            if constexpr (QD > 0) {
+                // row i + r + 2 out of its queue slot, the one after this step's request
+                q_slot = q_slot + 1 == QD ? 0 : q_slot + 1;
+                ring[S].q = *reinterpret_cast<const uint4 *>(P + 2 * 64 * PXN + q_slot * 256 + lane * 4);
+            } else {
 #ifdef VSZIP_DIAG_NO_LOAD  // (timing diagnostics only: the ring keeps what the band's fill put there)
-            if (next_off == 0xffffffffu) ring[S] = fetch_off(next_off);
+                if (next_off == 0xffffffffu) ring[S] = fetch_off(next_off);
 #else
-            ring[S] = fetch_off(next_off);
+                ring[S] = fetch_off(next_off);
 #endif
+            }
             // advance the refill row: plain bands just step down one row
 
         }
         // K_row of this row (used by the next step's store), then slide the K columns
         const uint32_t kr_cur = krow_now();
-        {
+        if constexpr (QD > 0) {
+            kcol += k_enter - k_leave;
+            k_new = k_new + 1 == G::KQ ? 0 : k_new + 1;
+            k_in = k_in + 1 == G::KQ ? 0 : k_in + 1;
+            k_out = k_out + 1 == G::KQ ? 0 : k_out + 1;
+        } else {
             constexpr int J = S % G::KL;
             kcol += kn[J] - ko[J];
 #ifndef VSZIP_DIAG_NO_KCOL  // (timing diagnostics only: wrong results)
@@ -734,12 +839,16 @@ struct RingWave {
         // branch that holds no memory instruction, so the vmcnt bookkeeping stays exact.
         if (plain) {
             next_off += srow;
-            kn_off += srow;
-            ko_off += srow;
+            if constexpr (QD == 0) {
+                kn_off += srow;
+                ko_off += srow;
+            }
         } else {
-            next_off = row_off(i + 2 + RV + G::D);
-            kn_off = row_off(i + 2 + RV + G::KL);
-            ko_off = row_off(i + 1 - RV + G::KL);
+            next_off = row_off(i + 2 + RV + G::AHEAD);
+            if constexpr (QD == 0) {
+                kn_off = row_off(i + 2 + RV + G::KL);
+                ko_off = row_off(i + 1 - RV + G::KL);
+            }
         }
 #ifndef VSZIP_DIAG_NO_FENCE  // (timing diagnostics only: wrong results)
         wave_lds_fence();
@@ -753,12 +862,12 @@ struct RingWave {
 };
 
 template <typename T, int R, bool GENERAL, int PXN = 8, bool HONLY = false>
-__global__ __launch_bounds__(64, (GENERAL ? 2 : RingGeom<R, (int)(sizeof(T) * PXN / 4), PXN, (HONLY ? 0 : R)>::WPE)) void boxblur_ct_ring_kernel(const RingParams prm) {
+__global__ __launch_bounds__(64, (GENERAL ? 2 : RingWave<T, R, GENERAL, PXN, HONLY>::G::WPE)) void boxblur_ct_ring_kernel(const RingParams prm) {
     using W = RingWave<T, R, GENERAL, PXN, HONLY>;
     using G = typename W::G;
     constexpr int RV = W::RV;
     static_assert(G::NR % 2 == 0 && G::NR <= 64, "ring period must be even and fit a wave");
-    __shared__ __attribute__((aligned(16))) uint32_t P[2 * 64 * PXN];
+    __shared__ __attribute__((aligned(16))) uint32_t P[G::LDS_BYTES / 4];  // prefix double buffer, then (QD > 0) the row queue and the K ring
 
     // XCD-aware remap: blocks b and b+8 share an XCD, so give every XCD one
     // contiguous chunk of the (plane, band, tile) list — neighbours share an L2.
@@ -818,7 +927,10 @@ __global__ __launch_bounds__(64, (GENERAL ? 2 : RingGeom<R, (int)(sizeof(T) * PX
     // descriptors: raw (stride 0), 32-bit data format; num_records = plane bytes (ring_ok keeps it < 4 GiB)
     st.rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(pl.src), 0, (int)((uint32_t)pl.h * st.srow), 0x00020000);
     st.rd = __builtin_amdgcn_make_buffer_rsrc(pl.dst, 0, (int)((uint32_t)pl.h * st.drow), 0x00020000);
-    st.plain = (y0 - RV >= 0) && (y0 + band_rows + RV + G::D + 2 < pl.h);
+    if constexpr (G::QD > 0)
+        st.plain = (y0 - RV >= 0) && (y0 + band_rows + RV <= pl.h);  // (rows past y0 + band_rows - 1 + r are never requested)
+    else
+        st.plain = (y0 - RV >= 0) && (y0 + band_rows + RV + G::D + 2 < pl.h);
 
     st.fill_all(y0, std::make_integer_sequence<int, G::NR>{});
 #pragma unroll
@@ -834,19 +946,43 @@ __global__ __launch_bounds__(64, (GENERAL ? 2 : RingGeom<R, (int)(sizeof(T) * PX
 #pragma unroll
         for (int k = 0; k < (int)G::K; ++k) acc += st.fetch_px(st.row_off(y0 - RV + k));
         st.kcol = acc;
+        if constexpr (G::QD == 0) {
 #pragma unroll
-        for (int j = 0; j < G::KL; ++j) {
-            st.kn[j] = st.fetch_px(st.row_off(y0 + j + 1 + RV));
-            st.ko[j] = st.fetch_px(st.row_off(y0 + j - RV));
+            for (int j = 0; j < G::KL; ++j) {
+                st.kn[j] = st.fetch_px(st.row_off(y0 + j + 1 + RV));
+                st.ko[j] = st.fetch_px(st.row_off(y0 + j - RV));
+            }
+            st.kn_off = st.row_off(y0 + G::KL + 1 + RV);
+            st.ko_off = st.row_off(y0 + G::KL - RV);
         }
-        st.kn_off = st.row_off(y0 + G::KL + 1 + RV);
-        st.ko_off = st.row_off(y0 + G::KL - RV);
         st.kr_prev = 0;
     }
-    st.next_off = st.row_off(y0 + 1 + RV + G::D);  // window rows y0-r .. y0+r+D are in the ring
+    st.next_off = st.row_off(y0 + 1 + RV + G::AHEAD);  // window rows y0-r .. y0+r+D are in the ring
     st.out_off = (uint32_t)y0 * st.drow;
 
     const int y1 = y0 + band_rows;
+    if constexpr (G::QD > 0) {
+        // Window row u (source row_off(y0 - r + u)) has K entry u mod KQ and, from u = 2r + 2 on, queue slot u mod QD. The ring holds u = 0 .. 2r + 1; the
+        // first step reads K entries 2r + 1 (entering) and 0 (leaving), moves u = 2r + 2 into the ring and requests u = 2r + 1 + QD. Everything before
+        // that is requested here — a band is at least one period, so none of it lies past the band — and has landed before the first step.
+        constexpr int QD = G::QD;
+        st.yend = y1;
+        st.q_lds = (uint32_t)(uintptr_t)P + 2 * 64 * PXN * 4;
+        st.k_lds = st.q_lds + QD * 1024;
+        st.kdoff = (uint32_t)lane * 16u;
+#pragma unroll 1
+        for (int u = 0; u <= 2 * RV + QD; ++u) {
+            const uint32_t off = st.row_off(y0 - RV + u);
+            ring_dma16_first<G::KB / 16>(st.rs, st.k_lds + (uint32_t)u * G::KB, st.kdoff, off);
+            if (u >= 2 * RV + 2) ring_dma16(st.rs, st.q_lds + (uint32_t)(u % QD) * 1024u, st.coff, off);
+        }
+        st.q_slot = (2 * RV + 1) % QD;
+        st.k_new = 2 * RV + 1 + QD;
+        st.k_in = 2 * RV + 1;
+        st.k_out = 0;
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __builtin_amdgcn_wave_barrier();
+    }
 #pragma unroll 1
     for (int i0 = y0; i0 < y1; i0 += G::NR) st.period(i0, y0, std::make_integer_sequence<int, G::NR>{});
     {
@@ -854,6 +990,8 @@ __global__ __launch_bounds__(64, (GENERAL ? 2 : RingGeom<R, (int)(sizeof(T) * PX
         st.window_sums(P + 64 * PXN, e);
         st.emit_row(e, st.out_off, st.kr_prev, true);
     }
+    // (the last requests, though out of range, still write this workgroup's LDS: they end before it is handed on)
+    if constexpr (G::QD > 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
 // ---------------------------------------------------------------------------
@@ -906,9 +1044,9 @@ struct RingSpan {
 };
 
 // Band length of a launch: every plane is cut into bands of about `target` ring periods (returned; *waves_out = the waves of that plan).
-template <typename T, int R, int PXN, bool HONLY = false>
+template <typename T, int R, int PXN, bool HONLY = false, bool GEN = false>
 int ring_plan(const vszip_plane *planes, const RingSpan *spans, int n, double *waves_ret) {
-    using G = typename RingWave<T, R, false, PXN, HONLY>::G;
+    using G = typename RingWave<T, R, GEN, PXN, HONLY>::G;
     // (the planes of a batch are a few geometries repeated — luma and chroma of every frame: the search below runs over the distinct ones, weighted)
     struct Geo {
         int h, ntx, count;
@@ -933,7 +1071,7 @@ int ring_plan(const vszip_plane *planes, const RingSpan *spans, int n, double *w
         // (tools/sweep_periods.sh: e.g. 64 4K frames — 19 periods: 4+2 equal bands, 3072 waves =
         // every slot, 603 us; 26: 635 us; 16: 1.17 generations, 710 us; 39: half the slots, 694 us).
         auto bands_for = [](int h, int P, int target) { return std::max((h % G::NR != 0 && P >= 2) ? 2 : 1, (P + target / 2) / target); };
-        const double halo_p = (double)(G::K - 1 + G::D) / G::NR;  // warm-up rows of a band, in periods
+        const double halo_p = (double)G::HALO_ROWS / G::NR;  // warm-up rows of a band, in periods
         const double slots = 256.0 * 4 * G::WPE;
         double waves_out = 0;
         auto cost_for = [&](int target) {
@@ -974,7 +1112,7 @@ int ring_plan(const vszip_plane *planes, const RingSpan *spans, int n, double *w
 // group inside the plane or its left mirror image (the caller's rule); GEN = true takes any width and any tile.
 template <typename T, int R, int PXN, bool GEN, bool HONLY = false>
 int launch_ct_ring_spans(vszip_ctx *ctx, const vszip_plane *all_planes, const RingSpan *all_spans, int nall) {
-    using G = typename RingWave<T, R, false, PXN, HONLY>::G;
+    using G = typename RingWave<T, R, GEN, PXN, HONLY>::G;  // (the two forms may differ in their ring period)
     std::vector<vszip_plane> planes_v;
     std::vector<RingSpan> spans_v;
     for (int i = 0; i < nall; ++i)
@@ -991,7 +1129,7 @@ int launch_ct_ring_spans(vszip_ctx *ctx, const vszip_plane *all_planes, const Ri
         const int n = std::min(kRingMaxPlanes, nplanes - done);
         auto bands_for = [](int h, int P, int target) { return std::max((h % G::NR != 0 && P >= 2) ? 2 : 1, (P + target / 2) / target); };
         double waves_out = 0;
-        int target = ring_plan<T, R, PXN, HONLY>(planes + done, spans + done, n, &waves_out);
+        int target = ring_plan<T, R, PXN, HONLY, GEN>(planes + done, spans + done, n, &waves_out);
         if (ctx->opt.ring_periods > 0) target = ctx->opt.ring_periods;  // development sweep knob (-DVSZIP_DEV_VARIANTS)
 #ifdef VSZIP_RING_PERIODS_FIXED  // (tools/variant.sh sweeps: one translation unit, no option)
         target = VSZIP_RING_PERIODS_FIXED;
@@ -1065,8 +1203,8 @@ constexpr int kRing16MaxR = 19;
 template <typename T, int R, bool HONLY = false>
 bool ring16_ok(const vszip_ctx *ctx, const vszip_plane *planes, int nplanes) {
     if (sizeof(T) != 1 || ctx->opt.ct_u8_px8) return false;
-    using G16 = RingGeom<R, 4, 16, (HONLY ? 0 : R)>;
-    using G8 = RingGeom<R, 2, 8, (HONLY ? 0 : R)>;
+    using G16 = RingGeom<R, 4, 16, (HONLY ? 0 : R), 0>;
+    using G8 = RingGeom<R, 2, 8, (HONLY ? 0 : R), 0>;
     double px = 0, t16 = 0, t8 = 0;
     for (int i = 0; i < nplanes; ++i) {
         const vszip_plane &p = planes[i];
