@@ -33,7 +33,10 @@
 //     per band; rows are prefetched D steps ahead; E_0's term is kept per wave
 //     from plane columns 0..r (two 1-pixel loads per step), which frees two
 //     lanes and makes 480 output columns per wave (3840 = 8 tiles, 1920 = 4,
-//     960 = 2); blockIdx is remapped so that neighbouring tiles/bands run on
+//     960 = 2); a plane's rows are cut into bands of equal row counts (to
+//     within one row; ring_bands.hpp), each at least one ring period, and a
+//     wave leaves its row loop behind its band's last row, so no output row
+//     is computed twice; blockIdx is remapped so that neighbouring tiles/bands run on
 //     one XCD and find their halo in that XCD's L2. 16-bit planes up to
 //     r = 13 take rows and K columns through a small queue in LDS instead
 //     (RingGeom::QD): loads that write LDS directly, one hand-counted wait a
@@ -46,6 +49,7 @@
 #include <utility>
 
 #include "plane_table.hpp"
+#include "ring_bands.hpp"
 
 namespace {
 
@@ -79,8 +83,7 @@ struct BBPlane {
     int w, h;
     int block0;  // first block index of this plane
     int ntx;     // column tiles
-    int nbands;  // row bands
-    int nperiods;  // ring kernel: ring periods covering the plane, ceil(h / NR), split evenly over the bands
+    int nbands;  // row bands (ring kernel: band by owns the rows [by * h / nbands, (by + 1) * h / nbands), ring_bands.hpp)
     int cx0;       // ring kernel: plane column of this launch's first tile (a plane may be split between two launches by columns)
 };
 
@@ -454,10 +457,11 @@ struct RingGeom {
 // All per-wave state of the ring kernel. step<S>() is instantiated once per ring
 // slot so that every ring index is a compile-time constant and the ring stays in
 // VGPRs (a runtime-indexed array would be demoted to scratch). A ring period is
-// straight-line code: bands are whole periods (the last band of a plane is
-// shifted up to end at the last row and recomputes a few rows of its neighbour,
-// writing identical values), so no step is conditional and every row load lands
-// directly in its slot, D steps before its first use.
+// straight-line code: no step is conditional and every row load lands directly
+// in its slot, D steps before its first use. A band is any number of rows, at
+// least one period (ring_bands.hpp): the row loop runs its whole periods, and
+// a second copy of the period behind the loop (last_period) runs the remaining
+// rows with a wave-uniform test between steps, so no row is done twice.
 //
 // GENERAL = false needs w % 8 == 0: lanes whose columns fall outside the plane hold
 // the edge-duplicating mirror image (hBlurInt's implicit padding, :139-158) of a
@@ -512,7 +516,7 @@ struct RingWave {
     uint32_t q_slot, k_new, k_in, k_out;
     uint32_t q_lds, k_lds;
     uint32_t kdoff;  // voffset of the K request: 16 * lane
-    int yend;
+    int yend;        // wave-uniform: one past the band's last row
     static constexpr uint32_t kOOB = 0xfffffff0u;
 
     __device__ __forceinline__ RawT fetch_off(uint32_t row_off) const {
@@ -859,6 +863,13 @@ struct RingWave {
     __device__ __forceinline__ void period(int i0, int y0, std::integer_sequence<int, S...>) {
         (step<S>(i0 + S, y0), ...);
     }
+    // The band's last, partial period: the same straight-line steps with a wave-uniform test between them, left behind the band's last row. It is a copy of
+    // the period's code outside the row loop on purpose: with the tests inside the loop (a loop with NR exits) hipcc keeps the wave-uniform row offsets in
+    // VGPRs and wraps every store in a readfirstlane loop.
+    template <int... S>
+    __device__ __forceinline__ void last_period(int i0, int y0, std::integer_sequence<int, S...>) {
+        (void)((i0 + S < yend && (step<S>(i0 + S, y0), true)) && ...);
+    }
 };
 
 template <typename T, int R, bool GENERAL, int PXN = 8, bool HONLY = false>
@@ -879,12 +890,12 @@ __global__ __launch_bounds__(64, (GENERAL ? 2 : RingWave<T, R, GENERAL, PXN, HON
     const int lb = b - pl.block0;
     const int tx = lb % pl.ntx;
     const int by = lb / pl.ntx;
-    // band `by` owns ring periods [by*P/nb, (by+1)*P/nb); the last band is shifted up to end
-    // at the last row (it recomputes < NR rows of its neighbour, writing identical values)
-    const int p0 = (int)((long)by * pl.nperiods / pl.nbands);
-    const int p1 = (int)((long)(by + 1) * pl.nperiods / pl.nbands);
-    const int band_rows = (p1 - p0) * G::NR;
-    const int y0 = min(p0 * G::NR, pl.h - band_rows);
+    // band `by` owns the rows [y0, y1), at least one ring period of them
+    // (the division runs on the vector unit; readfirstlane hands its wave-uniform result back to the scalar unit, where the row offsets, the loop tests and
+    // the soffset operands of the direct-to-LDS loads live)
+    const int y0 = __builtin_amdgcn_readfirstlane(ring_bands::band_y0(by, pl.h, pl.nbands));
+    const int y1 = __builtin_amdgcn_readfirstlane(ring_bands::band_y0(by + 1, pl.h, pl.nbands));
+    const int band_rows = y1 - y0;
     const int w = pl.w;
 
     W st;
@@ -943,8 +954,10 @@ __global__ __launch_bounds__(64, (GENERAL ? 2 : RingWave<T, R, GENERAL, PXN, HON
         st.kvo = (uint32_t)(kc * (int)sizeof(T));
         st.kwgt = lane < R ? 2u : (lane == R ? 1u : 0u);
         uint32_t acc = RV;
+        if constexpr (G::QD == 0) {  // (the queued form sums them out of its K ring, below: 2r + 1 pixel loads fewer in flight beside the ring's rows)
 #pragma unroll
-        for (int k = 0; k < (int)G::K; ++k) acc += st.fetch_px(st.row_off(y0 - RV + k));
+            for (int k = 0; k < (int)G::K; ++k) acc += st.fetch_px(st.row_off(y0 - RV + k));
+        }
         st.kcol = acc;
         if constexpr (G::QD == 0) {
 #pragma unroll
@@ -960,13 +973,12 @@ __global__ __launch_bounds__(64, (GENERAL ? 2 : RingWave<T, R, GENERAL, PXN, HON
     st.next_off = st.row_off(y0 + 1 + RV + G::AHEAD);  // window rows y0-r .. y0+r+D are in the ring
     st.out_off = (uint32_t)y0 * st.drow;
 
-    const int y1 = y0 + band_rows;
+    st.yend = y1;
     if constexpr (G::QD > 0) {
         // Window row u (source row_off(y0 - r + u)) has K entry u mod KQ and, from u = 2r + 2 on, queue slot u mod QD. The ring holds u = 0 .. 2r + 1; the
         // first step reads K entries 2r + 1 (entering) and 0 (leaving), moves u = 2r + 2 into the ring and requests u = 2r + 1 + QD. Everything before
         // that is requested here — a band is at least one period, so none of it lies past the band — and has landed before the first step.
         constexpr int QD = G::QD;
-        st.yend = y1;
         st.q_lds = (uint32_t)(uintptr_t)P + 2 * 64 * PXN * 4;
         st.k_lds = st.q_lds + QD * 1024;
         st.kdoff = (uint32_t)lane * 16u;
@@ -982,12 +994,18 @@ __global__ __launch_bounds__(64, (GENERAL ? 2 : RingWave<T, R, GENERAL, PXN, HON
         st.k_out = 0;
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __builtin_amdgcn_wave_barrier();
+        // the K columns' window sum: K entries 0 .. 2r hold the window rows y0 - r .. y0 + r
+        const T *kq = reinterpret_cast<const T *>(P + 2 * 64 * PXN + QD * 256);
+#pragma unroll
+        for (int u = 0; u <= 2 * RV; ++u) st.kcol += kq[u * (int)(G::KB / sizeof(T)) + st.kvo / sizeof(T)];
     }
+    int i0 = y0;
 #pragma unroll 1
-    for (int i0 = y0; i0 < y1; i0 += G::NR) st.period(i0, y0, std::make_integer_sequence<int, G::NR>{});
+    for (; i0 + G::NR <= y1; i0 += G::NR) st.period(i0, y0, std::make_integer_sequence<int, G::NR>{});
+    st.last_period(i0, y0, std::make_integer_sequence<int, G::NR - 1>{});  // (band_rows mod NR steps)
     {
-        uint32_t e[PXN];  // last row of the band: slot NR-1 wrote the odd buffer
-        st.window_sums(P + 64 * PXN, e);
+        uint32_t e[PXN];  // last row of the band: its step wrote the buffer of its slot's parity, (band_rows - 1) mod NR, and NR is even
+        st.window_sums(P + ((band_rows - 1) & 1) * (64 * PXN), e);
         st.emit_row(e, st.out_off, st.kr_prev, true);
     }
     // (the last requests, though out of range, still write this workgroup's LDS: they end before it is handed on)
@@ -1043,18 +1061,20 @@ struct RingSpan {
     int cx0, ntx;
 };
 
-// Band length of a launch: every plane is cut into bands of about `target` ring periods (returned; *waves_out = the waves of that plan).
+// Band length of a launch: every plane is cut into bands of about `target` ring periods (returned; *waves_ret = the waves of that plan). The search and
+// its cost model live in ring_bands.hpp; this is the instance's constants and the batch's distinct geometries.
+template <typename T, int R, int PXN, bool HONLY = false, bool GEN = false>
+constexpr ring_bands::Consts ring_consts() {
+    using G = typename RingWave<T, R, GEN, PXN, HONLY>::G;
+    return {G::NR, G::HALO_ROWS, 256 * 4 * G::WPE};
+}
 template <typename T, int R, int PXN, bool HONLY = false, bool GEN = false>
 int ring_plan(const vszip_plane *planes, const RingSpan *spans, int n, double *waves_ret) {
-    using G = typename RingWave<T, R, GEN, PXN, HONLY>::G;
-    // (the planes of a batch are a few geometries repeated — luma and chroma of every frame: the search below runs over the distinct ones, weighted)
-    struct Geo {
-        int h, ntx, count;
-    };
-    std::vector<Geo> geos;
+    // (the planes of a batch are a few geometries repeated — luma and chroma of every frame: the search runs over the distinct ones, weighted)
+    std::vector<ring_bands::Geo> geos;
     for (int i = 0; i < n; ++i) {
         bool found = false;
-        for (Geo &g : geos)
+        for (ring_bands::Geo &g : geos)
             if (g.h == planes[i].h && g.ntx == spans[i].ntx) {
                 ++g.count;
                 found = true;
@@ -1062,49 +1082,7 @@ int ring_plan(const vszip_plane *planes, const RingSpan *spans, int n, double *w
             }
         if (!found) geos.push_back({planes[i].h, spans[i].ntx, 1});
     }
-        // The choice
-        // trades re-read halo rows (2r+D per band: shorter bands = more traffic) against how well
-        // the waves fill the chip's wave slots over time: with W waves of up to max_len periods
-        // running in ceil(W / slots) generations, the fraction of slot-time doing work is
-        //     eff = total_work / (slots * generations * max_len),
-        // and measured launch times follow  total_work * (1 + 0.3 * (1 - eff))  within a few percent
-        // (tools/sweep_periods.sh: e.g. 64 4K frames — 19 periods: 4+2 equal bands, 3072 waves =
-        // every slot, 603 us; 26: 635 us; 16: 1.17 generations, 710 us; 39: half the slots, 694 us).
-        auto bands_for = [](int h, int P, int target) { return std::max((h % G::NR != 0 && P >= 2) ? 2 : 1, (P + target / 2) / target); };
-        const double halo_p = (double)G::HALO_ROWS / G::NR;  // warm-up rows of a band, in periods
-        const double slots = 256.0 * 4 * G::WPE;
-        double waves_out = 0;
-        auto cost_for = [&](int target) {
-            double work = 0, waves = 0, max_len = 0;
-            for (const Geo &g : geos) {
-                const int P = (g.h + G::NR - 1) / G::NR;
-                const int nb = bands_for(g.h, P, target);
-                const double ntx = (double)g.ntx * g.count;
-                work += ntx * (P + nb * halo_p);
-                waves += ntx * nb;
-                max_len = std::max(max_len, (double)((P + nb - 1) / nb) + halo_p);
-            }
-            waves_out = waves;
-            const double gens = std::ceil(waves / slots);
-            const double eff = std::min(1.0, work / (slots * gens * max_len));
-            // a launch that cannot fill the chip ends with its longest wave (a lone wave steps about
-            // three times as fast as one of a full chip): small inputs get many short bands
-            return std::max(work / slots * (1.0 + 0.3 * (1.0 - eff)), 0.3 * max_len);
-        };
-        // (small launches run out of the 256 MiB Infinity Cache and reward occupancy more than the
-        // model says: never go below 60 % of the slots when shorter bands can fill them)
-        int target = 1;
-        double best = cost_for(1);
-        const double min_waves = std::min(0.6 * slots, waves_out);
-        for (int t = 2; t <= 96; ++t) {
-            const double c = cost_for(t);
-            if (waves_out >= min_waves && c < best) {
-                best = c;
-                target = t;
-            }
-        }
-        *waves_ret = (cost_for(target), waves_out);
-        return target;
+    return ring_bands::plan_target(geos, ring_consts<T, R, PXN, HONLY, GEN>(), waves_ret);
 }
 
 
@@ -1127,7 +1105,6 @@ int launch_ct_ring_spans(vszip_ctx *ctx, const vszip_plane *all_planes, const Ri
     while (done < nplanes) {
         RingParams prm;
         const int n = std::min(kRingMaxPlanes, nplanes - done);
-        auto bands_for = [](int h, int P, int target) { return std::max((h % G::NR != 0 && P >= 2) ? 2 : 1, (P + target / 2) / target); };
         double waves_out = 0;
         int target = ring_plan<T, R, PXN, HONLY, GEN>(planes + done, spans + done, n, &waves_out);
         if (ctx->opt.ring_periods > 0) target = ctx->opt.ring_periods;  // development sweep knob (-DVSZIP_DEV_VARIANTS)
@@ -1135,8 +1112,10 @@ int launch_ct_ring_spans(vszip_ctx *ctx, const vszip_plane *all_planes, const Ri
         target = VSZIP_RING_PERIODS_FIXED;
 #endif
 #ifdef VSZIP_RING_PLAN_DEBUG  // (tools/variant.sh: what the band planner chose)
-        fprintf(stderr, "ring plan PX%d GEN%d r=%d: n=%d target=%d waves=%.0f slots=%d NR=%d | plane0 %dx%d ntx=%d\n", PXN, (int)GEN, R, n, target, waves_out, 256 * 4 * G::WPE, G::NR,
-                planes[done].w, planes[done].h, spans[done].ntx);
+        fprintf(stderr, "ring plan PX%d GEN%d r=%d: n=%d target=%d waves=%.0f slots=%d NR=%d | plane0 %dx%d ntx=%d bands=%d of %d..%d rows\n", PXN, (int)GEN, R, n, target, waves_out,
+                256 * 4 * G::WPE, G::NR, planes[done].w, planes[done].h, spans[done].ntx, ring_bands::bands_for(planes[done].h, G::NR, target),
+                planes[done].h / ring_bands::bands_for(planes[done].h, G::NR, target),
+                (planes[done].h + ring_bands::bands_for(planes[done].h, G::NR, target) - 1) / ring_bands::bands_for(planes[done].h, G::NR, target));
 #endif
         VSZIP_HIP_CHECK(ctx, hipSetDevice(ctx->device));
         int blocks = 0, fit = n;
@@ -1149,8 +1128,7 @@ int launch_ct_ring_spans(vszip_ctx *ctx, const vszip_plane *all_planes, const Ri
             d.dstride = (int)s.dst_stride;
             d.w = s.w;
             d.h = s.h;
-            d.nperiods = (s.h + G::NR - 1) / G::NR;
-            d.nbands = bands_for(s.h, d.nperiods, target);
+            d.nbands = ring_bands::bands_for(s.h, G::NR, target);
             d.ntx = spans[done + i].ntx;
             d.cx0 = spans[done + i].cx0;
             d.block0 = blocks;
