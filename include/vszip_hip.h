@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define VSZIP_ABI_VERSION 4 /* additive since 4: vszip_clahe, vszip_comb_mask, vszip_comb_mask_mt, vszip_checkmate, vszip_mosquito_nr, vszip_deband, vszip_deband_tables; 4 (round 5): vszip_dev_alloc searches a bounded number of candidates and keeps nothing (below); vszip_dev_arena_info added; vszip_dev_trim, vszip_dev_placement_info and
+#define VSZIP_ABI_VERSION 4 /* additive since 4: vszip_clahe, vszip_comb_mask, vszip_comb_mask_mt, vszip_checkmate, vszip_mosquito_nr, vszip_deband, vszip_deband_tables, vszip_bilateral_dither, vszip_bilateral_dither_derive, vszip_bilateral_dither_points; 4 (round 5): vszip_dev_alloc searches a bounded number of candidates and keeps nothing (below); vszip_dev_arena_info added; vszip_dev_trim, vszip_dev_placement_info and
                                vszip_dev_alloc_probed removed (nothing is searched for or parked any more); 3 (round 4): vszip_ctx_set_option / _get_option, vszip_dev_probe_region,
                                vszip_plane_average_async, vszip_plane_minmax_async added; 2 (round 3): vszip_ssim_source grew (YUV sources); entry points added since 1:
                                vszip_chain_run, vszip_ssimulacra2_src, vszip_to_rgbs_linear, vszip_probe_read_each, vszip_resample_table */
@@ -160,7 +160,9 @@ int vszip_probe_read_each(vszip_ctx *ctx, double *total_ms, int *launches, float
  *    its dst must not overlap src, only [0, w) x h of dst is written, and bases and pitches that are not multiples of four samples take a
  *    slower path with the same bits. Its offset tables and grain planes (vszip_deband_plane) are inputs under clauses 1-3 with the size of
  *    the entry's plane and pitches of their own: h x offsets_pitch pairs and h x grain_pitch samples readable each; no output depends on their
- *    padding either. Partial overlap is never allowed.
+ *    padding either. vszip_bilateral_dither reads a (2 radius - 1)^2 window mirrored at the plane's edges: its reads stay inside
+ *    [0, w) x h of src and ref, the whole point table (23 x K pairs) is an input, only [0, w) x h of dst is written, dst must overlap no
+ *    input, ref may be the very src pointer, and every base alignment and pitch takes the same path. Partial overlap is never allowed.
  */
 typedef struct vszip_plane {
     const void *src; /* input plane */
@@ -384,6 +386,62 @@ int vszip_deband_tables(const vszip_deband_cfg *cfg, vszip_deband_sizes *sizes, 
                         void *grain_c, uint32_t *grain_offsets, int32_t *max_offset, char *err, size_t err_cap);
 int vszip_deband(vszip_ctx *ctx, int dtype, const vszip_plane *planes, const vszip_deband_plane *per, int nplanes,
                  int sample_mode, int blur_first, float angle_boost, float max_angle, int max_offset);
+
+/*
+ * BilateralDither — the port of dither's Dither_bilateral16: replaces processPlane of src/filters/bilateral_dither.zig:34-213
+ * as called per plane by GetFrame(T).gf (src/vapoursynth/bilateral_dither.zig:52-110), the per-plane derivation of its create
+ * function (:151-209 with buildSlot :40-50) and generate of src/filters/bilateral_dither_subspl.zig:245-361.
+ *
+ * vszip_bilateral_dither_derive (device-free; replaces the derivation in create / buildSlot). One plane's wrapper arguments ->
+ * m = max(thr scale, unit), wmax = max(thr (1 - flat) scale, unit), sum_w_min = max(wmin wmax N, unit) in f32 in the reference's
+ * order (scale 2^(bits - 8) | 1/256, unit 1 | 1/65535 for integer | float clips; N = K sub-sampled, (2 radius - 1)^2 dense),
+ * `subsampled` (subspl >= 4 or subspl < 1e-3) and K (0 for the dense window). VSZIP_ERR_ARG with hz.getArray's wording in
+ * `err` (may be NULL) for radius [2..16384], thr [0..65535], flat [0..1], wmin [0..65535], subspl [0..4096]
+ * ("BilateralDither: radius value 1 is below minimum 2."), and for integer bits outside 8..16.
+ *
+ * vszip_bilateral_dither_points (device-free; replaces subspl.generate with r_h == r_v == radius). Fills `points` (HOST memory,
+ * `capacity` pairs, at least 23 K) with the 23 lists of K (x, y) int16 pairs, list after list; *K as derive gives it. points ==
+ * NULL only returns K. Every list starts with (0, 0), holds no point twice and lies in [-(radius - 1), radius - 1]^2. The
+ * void-and-cluster matrix of the lists with K >= 32 is built once a call.
+ *
+ * vszip_bilateral_dither. dtype VSZIP_U8 (bits_per_sample 8), VSZIP_U16 (9..16) or VSZIP_F32; planes[i].src / dst, and
+ * planes[i].ref (optional, same size, its own pitch) as the plane that drives the weights; per_plane[i] beside planes[i]:
+ *   radius            one radius per plane, as the reference's wrapper passes it (rh == rv), 2..16384, <= w and <= h;
+ *   m, wmax, sum_w_min  from vszip_bilateral_dither_derive;
+ *   points, K         DEVICE pointer to the 23 K pairs of vszip_bilateral_dither_points and K (3..4096): the sub-sampled path;
+ *                     NULL and 0: the dense window.
+ * Per output sample the taps are taken in the reference's order (dense: rows outer; sub-sampled: the points of list
+ * (start(y) + (x >> 2)) % 23 in list order), each wgt = max(min(m - |vr - cen_ref|, wmax), 0), sum_w += wgt,
+ * sum = fmaf(v - cen, wgt, sum); the result cen + sum / max(sum_w, sum_w_min) is clamped to [0, 2^bits - 1] and rounded half
+ * away from zero for integers and stored as it is for float. Bit-exact with the reference in all three sample types. Two
+ * paths: a workgroup stages its tile and a halo of radius - 1 samples, already mirrored, in LDS (and a second tile for
+ * `ref`), or gathers from global memory with the mirror applied per tap (any radius); VSZIP_BILATERAL_DITHER_PATH
+ * (csrc/options.inc) forces one, and a forced tile that does not fit takes the global path. A call is split into launches by
+ * planes and row bands of a bounded number of taps each. Differences from the reference: the dense window serves radius <= 128
+ * (VSZIP_ERR_UNSUPPORTED above; the sub-sampled path serves every radius), and the 16 x 16 minimum of the clip is the host's
+ * check. VSZIP_ERR_ARG: 'BilateralDither: picture size must be greater than "radius"' for w or h below the radius, a radius
+ * out of range, K > 0 without points (or points with K outside 3..4096), a NULL src or dst, a dst that is the src or ref pointer (any other overlap
+ * is the caller's to avoid).
+ * Asynchronous on the context stream. "Plane memory": reads stay inside [0, w) x h of src and ref; the whole point table is an
+ * input; only [0, w) x h of dst is written.
+ */
+typedef struct vszip_bilateral_dither_cfg {
+    float m, wmax, sum_w_min;
+    int32_t K;          /* points per list; 0: the dense window */
+    int32_t subsampled; /* 1: the sub-sampled path (needs the point lists) */
+} vszip_bilateral_dither_cfg;
+typedef struct vszip_bilateral_dither_plane {
+    int32_t radius;
+    float m, wmax, sum_w_min;
+    const int16_t *points; /* device: 23 lists of K (x, y) pairs; NULL: dense */
+    int32_t K;
+} vszip_bilateral_dither_plane;
+
+int vszip_bilateral_dither_derive(int is_float, int bits_per_sample, int radius, float thr, float flat, float wmin, float subspl,
+                                  vszip_bilateral_dither_cfg *out, char *err, size_t err_cap);
+int vszip_bilateral_dither_points(int radius, float subspl, int16_t *points, size_t capacity, int32_t *K);
+int vszip_bilateral_dither(vszip_ctx *ctx, int dtype, int bits_per_sample, const vszip_plane *planes,
+                           const vszip_bilateral_dither_plane *per_plane, int nplanes);
 
 /*
  * PlaneMinMax — replaces filter.minMax / minMaxRef / minMaxNoThr / minMaxNoThrRef

@@ -65,6 +65,16 @@ class DebandPlane(C.Structure):
                 ("thr", C.c_float), ("thr1", C.c_float), ("thr2", C.c_float), ("lo", C.c_float), ("hi", C.c_float)]
 
 
+class BilateralDitherCfg(C.Structure):
+    """vszip_bilateral_dither_cfg"""
+    _fields_ = [("m", C.c_float), ("wmax", C.c_float), ("sum_w_min", C.c_float), ("K", C.c_int32), ("subsampled", C.c_int32)]
+
+
+class BilateralDitherPlane(C.Structure):
+    """vszip_bilateral_dither_plane"""
+    _fields_ = [("radius", C.c_int32), ("m", C.c_float), ("wmax", C.c_float), ("sum_w_min", C.c_float), ("points", C.c_void_p), ("K", C.c_int32)]
+
+
 class BilateralCfg(C.Structure):
     _fields_ = [
         ("sigmaS", C.c_double), ("sigmaR", C.c_double), ("process", C.c_int32), ("algorithm", C.c_int32),
@@ -154,6 +164,9 @@ SYMBOLS = {
     "vszip_mosquito_nr": (_i, [_vp, _i, _i, _PP, _i, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_uint8)]),
     "vszip_deband_tables": (_i, [C.POINTER(DebandCfg), C.POINTER(DebandSizes), _vp, _vp, _vp, _vp, _vp, C.POINTER(C.c_int32), C.c_char_p, _sz]),
     "vszip_deband": (_i, [_vp, _i, _PP, C.POINTER(DebandPlane), _i, _i, _i, C.c_float, C.c_float, _i]),
+    "vszip_bilateral_dither_derive": (_i, [_i, _i, _i, C.c_float, C.c_float, C.c_float, C.c_float, C.POINTER(BilateralDitherCfg), C.c_char_p, _sz]),
+    "vszip_bilateral_dither_points": (_i, [_i, C.c_float, _vp, _sz, C.POINTER(C.c_int32)]),
+    "vszip_bilateral_dither": (_i, [_vp, _i, _i, _PP, C.POINTER(BilateralDitherPlane), _i]),
     "vszip_plane_average": (_i, [_vp, _i, _PP, _i, C.POINTER(C.c_int32), _i, _i, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "vszip_plane_minmax": (_i, [_vp, _i, _PP, _i, C.c_float, C.c_float, _i, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "vszip_plane_average_async": (_i, [_vp, _i, _PP, _i, C.POINTER(C.c_int32), _i, _i, _vp]),
@@ -202,6 +215,29 @@ def deband_tables(width, height, ssw=0, ssh=0, num_frames=1, range=15, sample_mo
     if rc != 0:
         raise ValueError(err.value.decode() or f"vszip_deband_tables -> {rc}")
     return dict(luma=luma, chroma=chroma, grain_y=gy, grain_c=gc, grain_offsets=offs, max_offset=mx.value, items=sizes.grain_items // (3 if dynamic_grain else 1))
+
+
+def bilateral_dither_params(is_float, bits, radius=16, thr=2.5, flat=0.4, wmin=0.0, subspl=0.0) -> dict:
+    """vszip_bilateral_dither_derive (device-free): one plane's wrapper arguments -> m, wmax, sum_w_min (np.float32), K (0: the dense window) and
+    subsampled. ValueError with the reference's wording for an argument out of range."""
+    cfg, err = BilateralDitherCfg(), C.create_string_buffer(256)
+    rc = load().vszip_bilateral_dither_derive(int(bool(is_float)), int(bits), int(radius), float(thr), float(flat), float(wmin), float(subspl), C.byref(cfg), err, len(err))
+    if rc != 0:
+        raise ValueError(err.value.decode() or f"vszip_bilateral_dither_derive -> {rc}")
+    return dict(m=np.float32(cfg.m), wmax=np.float32(cfg.wmax), sum_w_min=np.float32(cfg.sum_w_min), K=int(cfg.K), subsampled=bool(cfg.subsampled))
+
+
+def bilateral_dither_points(radius, subspl=0.0) -> np.ndarray:
+    """vszip_bilateral_dither_points (device-free): the 23 point lists of a geometry as a (23, K, 2) int16 array, [..., 0] = x, [..., 1] = y"""
+    lib, k = load(), C.c_int32()
+    rc = lib.vszip_bilateral_dither_points(int(radius), float(subspl), None, 0, C.byref(k))
+    if rc != 0:
+        raise ValueError(f"vszip_bilateral_dither_points({radius}, {subspl}) -> {rc}")
+    pts = np.empty((23, k.value, 2), np.int16)
+    rc = lib.vszip_bilateral_dither_points(int(radius), float(subspl), pts.ctypes.data, 23 * k.value, C.byref(k))
+    if rc != 0:
+        raise ValueError(f"vszip_bilateral_dither_points({radius}, {subspl}) -> {rc}")
+    return pts
 
 
 def _share_torch_hip_runtime():
@@ -651,6 +687,32 @@ class Device:
     def prepared_deband(self, srcs, dsts, entries, sample_mode=2, blur_first=True, angle_boost=1.5, max_angle=0.15, max_offset=128):
         """-> a callable queueing vszip_deband on argument blocks built once."""
         fn, ctx, check, args = self.lib.vszip_deband, self.ctx, self.check, self._deband_args(srcs, dsts, entries, sample_mode, blur_first, angle_boost, max_angle, max_offset)
+        return lambda: check(fn(ctx, *args))
+
+    def upload_bilateral_dither_points(self, pts: np.ndarray) -> DevPlane:
+        """the (23, K, 2) int16 lists of bilateral_dither_points() (or of the numpy spec) as one row of 23 * K * 2 values on the device"""
+        return self.upload(np.ascontiguousarray(pts, np.int16).reshape(1, -1))
+
+    def bilateral_dither_entry(self, radius, m, wmax, sum_w_min, points=None, K=0) -> BilateralDitherPlane:
+        """one vszip_bilateral_dither_plane: m / wmax / sum_w_min / K of bilateral_dither_params(), `points` the DevPlane of
+        upload_bilateral_dither_points (None: the dense window)"""
+        return BilateralDitherPlane(int(radius), float(m), float(wmax), float(sum_w_min), points.ptr if points is not None else None, int(K))
+
+    def _bilateral_dither_args(self, srcs, dsts, entries, refs, bits):
+        n = len(srcs)
+        if len(entries) != n or len(dsts) != n or (refs is not None and len(refs) != n):
+            raise ValueError("bilateral_dither: one destination, one vszip_bilateral_dither_plane entry (and one ref or None) per plane")
+        dt = srcs[0].dtype
+        return (_NP2DT[dt], int(bits) if bits is not None else 8 * dt.itemsize, self.plane_table(srcs, dsts, refs), (BilateralDitherPlane * n)(*entries), n)
+
+    def bilateral_dither(self, srcs, dsts, entries, refs=None, bits=None):
+        """vszip.BilateralDither on every plane of srcs (u8, u16 with `bits` 9..16, or f32; any sizes): entries[i] (bilateral_dither_entry) names
+        plane i's radius, weights and point lists; refs[i] (optional) drives the weights. dsts must overlap no input."""
+        self.check(self.lib.vszip_bilateral_dither(self.ctx, *self._bilateral_dither_args(srcs, dsts, entries, refs, bits)))
+
+    def prepared_bilateral_dither(self, srcs, dsts, entries, refs=None, bits=None):
+        """-> a callable queueing vszip_bilateral_dither on argument blocks built once."""
+        fn, ctx, check, args = self.lib.vszip_bilateral_dither, self.ctx, self.check, self._bilateral_dither_args(srcs, dsts, entries, refs, bits)
         return lambda: check(fn(ctx, *args))
 
     def prepared_limit_filter(self, flts, srcs, dsts, dark_thr, bright_thr, elast):

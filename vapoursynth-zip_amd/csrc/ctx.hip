@@ -88,6 +88,7 @@ const OptionRange kRanges[] = {
     {"VSZIP_RING_PERIODS", 0, 1 << 16},
     {"VSZIP_CLAHE_SCRATCH_MIB", 1, 1 << 20},
     {"VSZIP_DEBAND_SCRATCH_MIB", 1, 1 << 20}, {"VSZIP_DEBAND_PATH", 0, 2},
+    {"VSZIP_BILATERAL_DITHER_PATH", 0, 2},
 };
 bool option_in_range(const char *env, int v) {
     for (const OptionRange &r : kRanges)

@@ -322,3 +322,248 @@ VSZIP_EXPORT int vszip_deband_tables(const vszip_deband_cfg *cfg, vszip_deband_s
     }
     return VSZIP_OK;
 }
+
+// ---------------------------------------------------------------------------------------------------------
+// BilateralDither: the create-time derivation of src/vapoursynth/bilateral_dither.zig:151-209 (buildSlot :40-50) and
+// the point lists of src/filters/bilateral_dither_subspl.zig:245-361. The derivation is f32 arithmetic in the
+// reference's order. The lists: 23 per geometry, K points each, the first always (0, 0); under 32 points a 4-arm
+// spiral whose start angle comes from minstd_rand0 and whose gaps an LCG fills, from 32 points on a scan of a
+// toroidal void-and-cluster matrix at an offset from minstd_rand0, levels [0, trg) first and then one a pass.
+// ---------------------------------------------------------------------------------------------------------
+namespace {
+constexpr int kBdLists = 23, kBdMaxPoints = 4096, kBdSpiralBelow = 32, kBdKernel = 9;
+
+int bd_round_f32(double x) { return (int)std::nearbyintf((float)x); }  // fstb::round_int: to nearest, ties to even
+int bd_clamp(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
+uint32_t bd_lcg(uint32_t v) { return v * 1664525u + 1013904223u; }
+
+struct BdMinstd {  // libstdc++'s default_random_engine with uniform_int_distribution<int>(0, n - 1)
+    uint32_t s = 1;
+    int dist(int n) {
+        const uint32_t scaling = 2147483645u / (uint32_t)n, past = (uint32_t)n * scaling;
+        uint32_t ret;
+        do {
+            s = (uint32_t)(((uint64_t)s * 16807u) % 2147483647u);
+            ret = s - 1;
+        } while (ret >= past);
+        return (int)(ret / scaling);
+    }
+};
+
+// a square matrix addressed modulo its size
+template <typename T>
+struct BdTorus {
+    int n;
+    std::vector<T> d;
+    explicit BdTorus(int size) : n(size), d((size_t)size * size, T(0)) {}
+    size_t at(int x, int y) const { return (size_t)(((y % n) + n) % n) * n + (size_t)(((x % n) + n) % n); }
+    T get(int x, int y) const { return d[at(x, y)]; }
+    T &ref(int x, int y) { return d[at(x, y)]; }
+};
+
+struct BdPos {
+    int x, y;
+};
+
+// the first cell in scan order, among those of `color`, with the largest Gaussian sum over its neighbours of the same colour
+BdPos bd_find_cluster(const BdTorus<uint16_t> &m, const double (&kern)[kBdKernel][kBdKernel], uint16_t color) {
+    double best = -1.0;
+    BdPos at{0, 0};
+    constexpr int kh = (kBdKernel - 1) / 2;
+    for (int y = 0; y < m.n; ++y)
+        for (int x = 0; x < m.n; ++x) {
+            if (m.get(x, y) != color) continue;
+            double sum = 0.0;
+            for (int j = -kh; j <= kh; ++j)
+                for (int i = -kh; i <= kh; ++i)
+                    if (m.get(x + i, y + j) == color) sum += kern[j + kh][i + kh];
+            if (sum > best) {
+                best = sum;
+                at = BdPos{x, y};
+            }
+        }
+    return at;
+}
+
+// the rank of every cell, 0 .. n * n - 1; depends on the size alone
+BdTorus<uint16_t> bd_vnc_matrix(int n) {
+    constexpr int kh = (kBdKernel - 1) / 2;
+    double kern[kBdKernel][kBdKernel];
+    const double inv2s2 = 1.0 / (2.0 * 1.5 * 1.5);
+    for (int j = -kh; j <= kh; ++j)
+        for (int i = -kh; i <= kh; ++i) kern[j + kh][i + kh] = std::exp(-(double)(i * i + j * j) * inv2s2);
+
+    // a 10 % pattern by serpentine error diffusion, two passes
+    BdTorus<uint16_t> base(n);
+    BdTorus<double> err(n);
+    int dir = 1;
+    for (int pass = 0; pass < 2; ++pass)
+        for (int y = 0; y < n; ++y) {
+            for (int x = dir < 0 ? n - 1 : 0; x != (dir < 0 ? -1 : n); x += dir) {
+                const double val = 0.1 + err.get(x, y);
+                err.ref(x, y) = 0.0;
+                const int q = bd_clamp(bd_round_f32(val), 0, 1);
+                base.ref(x, y) = (uint16_t)q;
+                const double e = val - (double)q;
+                err.ref(x + dir, y) += e * 0.5;
+                err.ref(x - dir, y + 1) += e * 0.25;
+                err.ref(x, y + 1) += e * 0.25;
+            }
+            dir = -dir;
+        }
+    // move the tightest cluster's cell into the largest void until they are the same cell
+    for (;;) {
+        const BdPos c = bd_find_cluster(base, kern, 1);
+        base.ref(c.x, c.y) = 0;
+        const BdPos v = bd_find_cluster(base, kern, 0);
+        base.ref(v.x, v.y) = 1;
+        if (c.x == v.x && c.y == v.y) break;
+    }
+    int ones = 0;
+    for (uint16_t v : base.d) ones += v == 1;
+    BdTorus<uint16_t> vnc(n);
+    {
+        BdTorus<uint16_t> mat = base;
+        for (int rank = ones; rank > 0;) {
+            --rank;
+            const BdPos c = bd_find_cluster(mat, kern, 1);
+            mat.ref(c.x, c.y) = 0;
+            vnc.ref(c.x, c.y) = (uint16_t)rank;
+        }
+    }
+    {
+        BdTorus<uint16_t> mat = base;
+        for (int rank = ones; rank < n * n; ++rank) {
+            const BdPos v = bd_find_cluster(mat, kern, 0);
+            mat.ref(v.x, v.y) = 1;
+            vnc.ref(v.x, v.y) = (uint16_t)rank;
+        }
+    }
+    return vnc;
+}
+
+int bd_points_k(int radius, float subspl, double *actual_out) {
+    const double s = (double)subspl, area = (double)((2 * radius - 1) * (2 * radius - 1));
+    const double actual = s < 1e-3 ? (double)(2 * radius) : s;
+    if (actual_out) *actual_out = actual;
+    return bd_clamp(bd_round_f32(area / actual), 3, kBdMaxPoints);
+}
+
+// Zig's {d} of an f32: integers without a point, other values in the shortest decimal form that reads back as the same float
+void bd_fmt(char *out, size_t cap, float v) {
+    if (v == std::floor(v) && std::fabs(v) < 1e15f) {
+        std::snprintf(out, cap, "%.0f", (double)v);
+        return;
+    }
+    for (int p = 1; p <= 9; ++p) {
+        std::snprintf(out, cap, "%.*g", p, (double)v);
+        if (std::strtof(out, nullptr) == v) return;
+    }
+}
+
+int bd_range_error(char *err, size_t cap, const char *key, float v, float lo, float hi) {
+    if (err && cap) {
+        char a[64], b[64];
+        bd_fmt(a, sizeof a, v);
+        bd_fmt(b, sizeof b, v < lo ? lo : hi);
+        std::snprintf(err, cap, "BilateralDither: %s value %s is %s %s.", key, a, v < lo ? "below minimum" : "above maximum", b);
+    }
+    return VSZIP_ERR_ARG;
+}
+}  // namespace
+
+VSZIP_EXPORT int vszip_bilateral_dither_derive(int is_float, int bits, int radius, float thr, float flat, float wmin, float subspl,
+                                               vszip_bilateral_dither_cfg *out, char *err, size_t err_cap) {
+    if (err && err_cap) err[0] = 0;
+    if (!out) return VSZIP_ERR_ARG;
+    if (!is_float && (bits < 8 || bits > 16)) {
+        if (err && err_cap) std::snprintf(err, err_cap, "BilateralDither: integer input must be 8..16 bit");
+        return VSZIP_ERR_ARG;
+    }
+    // hz.getArray's checks, in the create function's order
+    if (radius < 2 || radius > 16384) return bd_range_error(err, err_cap, "radius", (float)radius, 2, 16384);
+    struct Check {
+        const char *key;
+        float v, lo, hi;
+    } const checks[] = {{"thr", thr, 0, 65535}, {"flat", flat, 0, 1}, {"wmin", wmin, 0, 65535}, {"subspl", subspl, 0, 4096}};
+    for (const Check &c : checks)
+        if (!(c.v >= c.lo && c.v <= c.hi)) return bd_range_error(err, err_cap, c.key, c.v, c.lo, c.hi);
+    const float scale = is_float ? 1.0f / 256.0f : (float)(1u << (bits - 8));
+    const float unit = is_float ? 1.0f / 65535.0f : 1.0f;
+    out->m = std::max(thr * scale, unit);
+    const float t = thr * (1.0f - flat);
+    out->wmax = std::max(t * scale, unit);
+    out->subsampled = subspl >= 4.0f || (double)subspl < 1e-3;
+    out->K = out->subsampled ? bd_points_k(radius, subspl, nullptr) : 0;
+    const float n = out->subsampled ? (float)out->K : (float)((2 * radius - 1) * (2 * radius - 1));
+    const float ww = wmin * out->wmax;
+    out->sum_w_min = std::max(ww * n, unit);
+    return VSZIP_OK;
+}
+
+VSZIP_EXPORT int vszip_bilateral_dither_points(int radius, float subspl, int16_t *points, size_t capacity, int32_t *K_out) {
+    if (radius < 2 || radius > 16384 || !(subspl >= 0.0f && subspl <= 4096.0f)) return VSZIP_ERR_ARG;
+    double actual;
+    const int K = bd_points_k(radius, subspl, &actual);
+    if (K_out) *K_out = K;
+    if (!points) return VSZIP_OK;  // the query
+    if (capacity < (size_t)kBdLists * K) return VSZIP_ERR_ARG;
+    const int r = radius, win = 2 * r - 1;
+    const int n = bd_clamp(win * 3 / 2, 16, 32);
+    BdTorus<uint16_t> vnc(K >= kBdSpiralBelow ? n : 1);
+    if (K >= kBdSpiralBelow) vnc = bd_vnc_matrix(n);  // once a call
+    BdMinstd ms_a, ms_x, ms_y;
+    uint32_t rnd = 1;
+    // (K < 32 means win * win < 4096 * 32; K >= 32 visits the window cell by cell)
+    std::vector<char> done((size_t)win * win);
+    const double pi = 3.1415926535897932384626433832795;
+    for (int lc = 0; lc < kBdLists; ++lc) {
+        int16_t *cur = points + (size_t)lc * K * 2;
+        std::fill(done.begin(), done.end(), 0);
+        cur[0] = cur[1] = 0;
+        done[(size_t)(r - 1) + (size_t)(r - 1) * win] = 1;
+        int cnt = 1;
+        auto put = [&](int x, int y) {
+            const size_t da = (size_t)(x + r - 1) + (size_t)(y + r - 1) * win;
+            if (done[da]) return;
+            cur[2 * cnt] = (int16_t)x;
+            cur[2 * cnt + 1] = (int16_t)y;
+            done[da] = 1;
+            ++cnt;
+        };
+        if (K < kBdSpiralBelow) {
+            const double angle_base = (double)ms_a.dist(kBdLists) * (pi * 0.5 / (double)kBdLists);
+            const int arm_dir = 1 - (lc & 2), narm = 4, npa = (K - 1) / narm;
+            const double amul = 2.0 * pi / (double)narm * (double)arm_dir;
+            for (int p = 0; p < npa; ++p) {
+                const double posd = std::pow((double)p / (double)npa, 3.0 / 5.0);
+                for (int a = 0; a < narm; ++a) {
+                    const double ang = angle_base + (posd * 2.0 + (double)a) * amul;
+                    const int x = bd_round_f32(std::cos(ang) * posd * (double)(r - 1));
+                    const int y = bd_round_f32(std::sin(ang) * posd * (double)(r - 1));
+                    if (x > -r && x < r && y > -r && y < r) put(x, y);
+                }
+            }
+            while (cnt < K) {
+                rnd = bd_lcg(rnd);
+                const int x = (int)((rnd >> 8) % (uint32_t)win) - (r - 1);
+                rnd = bd_lcg(rnd);
+                const int y = (int)((rnd >> 8) % (uint32_t)win) - (r - 1);
+                put(x, y);
+            }
+        } else {
+            const int ofs_x = ms_x.dist(win), ofs_y = ms_y.dist(win);
+            int lo = 0, hi = (int)std::floor((double)(n * n) / actual);
+            while (cnt < K) {
+                for (int y = 0; y < win && cnt < K; ++y)
+                    for (int x = 0; x < win && cnt < K; ++x) {
+                        const int v = vnc.get(x + ofs_x, y + ofs_y);
+                        if (v >= lo && v < hi) put(x - (r - 1), y - (r - 1));
+                    }
+                lo = hi;
+                ++hi;
+            }
+        }
+    }
+    return VSZIP_OK;
+}

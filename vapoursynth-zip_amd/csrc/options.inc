@@ -38,6 +38,7 @@ VSZIP_OPT(eedi3_no_overlap, "VSZIP_EEDI3_NO_OVERLAP", 0)
 VSZIP_OPT(minmax_no_predict, "VSZIP_MINMAX_NO_PREDICT", 0)   // thresholded PlaneMinMax on 16-bit / float planes: always the two sweeps (no single-read sweep over the ranges the previous call of the same shape predicts)
 VSZIP_OPT(ssim_no_yuv420_lds, "VSZIP_SSIM_NO_YUV420_LDS", 0)  // SSIMULACRA2 on 4:2:0 / 4:2:2 / 4:4:4 integer clips: the fused tile kernel (what the other YUV formats take) instead of the persistent pre-stage passes with the transfer table in LDS + the f32 pyramid pass (rounds 5, 6)
 VSZIP_OPT(deband_path, "VSZIP_DEBAND_PATH", 0)            // Deband gathers: 0 by the call's max_offset (LDS tile up to 32, else global memory), 1 the LDS tile wherever its halo covers max_offset, 2 always global memory
+VSZIP_OPT(bilateral_dither_path, "VSZIP_BILATERAL_DITHER_PATH", 0)  // BilateralDither taps: 0 the LDS tile where tile + halo (+ ref tile) fit its LDS budget, else global memory; 1 the LDS tile wherever it fits; 2 always global memory
 
 // ---- development variants (measured losers and sweep knobs) ----
 // (round 5: selectors whose alternative is never the faster one on any geometry of tools/cliff_sweep.py; the kernels that geometry rules still route to stay in the default build, only the switch that FORCES them is a development variant)
