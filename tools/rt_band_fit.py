@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Round 4: grid search of the band-count cost model (boxblur_rt.hip ichain_band_rows) against tools/rt_band_sweep.py output (gpurun_out/r4_rt_band_sweep.txt)."""
+"""Round 4: grid search of the band-count cost model (rt_plan.hpp ichain_band_rows) against tools/rt_band_sweep.py output (profiles/r04_rt_band_sweep.txt)."""
 import re, itertools, math
 rows=[]
 for l in open('profiles/r04_rt_band_sweep.txt'):

@@ -14,11 +14,15 @@
 #include <vector>
 
 #include "plane_table.hpp"
+#include "rt_plan.hpp"
 
 // boxblur.hip: one integer row pass of r <= 22 through the ring kernel (VSZIP_ERR_UNSUPPORTED: not for these planes)
 int vszip_bb_ct_row_pass(vszip_ctx *ctx, int dtype, int r, const vszip_plane *planes, int nplanes);
 
 namespace {
+
+// chain, hsmall and vsmall geometry: one definition for the kernels and the planner's predicates (rt_plan.hpp)
+using rt_plan::kFcMaxPass, rt_plan::kFcPf, rt_plan::kFcRB, rt_plan::kHsMaxR, rt_plan::kHsMaxW, rt_plan::kHsHalo, rt_plan::kVsMaxR;
 
 struct RPlane {
     const void *src;
@@ -912,7 +916,6 @@ struct FChain {
     __device__ __forceinline__ int first_interior() const { return P * L + R + 1; }
 };
 
-constexpr int kFcPf = 32;
 // Vertical: lane = column, the plane's rows are the ticks. Columns are the only parallelism a running sum leaves (about one wave per SIMD on 8 4K frames),
 // so what counts is a wave's own time per tick, and a wave hides the memory latency itself: three register sets of kFcPf rows rotate — one is summed
 // while two are in flight. One load instruction fetches FOUR rows (16 lanes x 4 samples each) and one store writes four, through LDS both ways: with a
@@ -1218,7 +1221,6 @@ __global__ __launch_bounds__(64) void boxblur_rt_ichain_kernel(const RParams prm
 // Horizontal: lane = row for the chain, lane = column for memory: 64 source columns of the wave's 64 rows enter through one LDS tile, the last stage's
 // outputs leave through another, flushed whenever its 64 columns are complete. All 64 lanes carry a row (the per-pass kernel takes 16 rows a wave for
 // more waves; here a wave's time is the line's ticks times the cost of a tick whatever its row count, and a SIMD runs two waves no faster than one).
-constexpr int kFcRB = 64;
 template <typename T, int P>
 __global__ __launch_bounds__(64) void boxblur_rt_float_hchain_kernel(const RParams prm) {
     constexpr int RB = kFcRB;
@@ -1456,8 +1458,6 @@ __global__ __launch_bounds__(kHmNT) void boxblur_rt_hmulti_kernel(const RParams 
 // slides it — blurInt's closed form (:10-41, see RtVec above): dst[x] = (inv2 * E_x + 32768 + ((E_0 * invlo) >> 16)) >> 16 with E_0 read from
 // the row's first R + 1 samples of the pass's own input, which are right there. One read and one write of the plane for all passes.
 // ---------------------------------------------------------------------------------------------
-constexpr int kHsMaxR = 16, kHsMaxW = 8192, kHsHalo = 16;  // (radius 13 x 5 passes is the reference README's third benchmark)
-[[maybe_unused]] constexpr int kVsMaxR = 8;
 template <typename T, int R>
 __global__ __launch_bounds__(64) void boxblur_rt_hsmall_kernel(const RParams prm, const int npass, const int pitch /* u16 elements per LDS buffer */) {
     extern __shared__ __attribute__((aligned(16))) uint16_t hs[];
@@ -1777,15 +1777,6 @@ __global__ __launch_bounds__(256) void rt_transpose_kernel(const RParams prm) {
 }
 
 #endif  // VSZIP_DEV_VARIANTS
-// all horizontal passes of a small radius in one launch (boxblur_rt_hsmall_kernel); false: the planes do not qualify
-template <typename T>
-bool hsmall_ok(const vszip_ctx *ctx, const std::vector<RPlane> &pl, int radius, int npass) {
-    if (!std::is_integral<T>::value || sizeof(T) > 2 || npass < 2 || radius < 1 || radius > kHsMaxR || ctx->opt.rt_no_hsmall) return false;
-    for (const RPlane &q : pl) {
-        if (!rt_aligned<T>(q) || q.w <= 2 * radius || q.w > kHsMaxW || q.sstride < ((q.w + 7) / 8) * 8 || q.dstride < ((q.w + 7) / 8) * 8) return false;
-    }
-    return true;
-}
 template <typename T>
 int launch_hsmall(vszip_ctx *ctx, const std::vector<RPlane> &pl, int radius, int npass, bool keep) {
     RParams prm = rt_table(radius, keep);
@@ -1812,24 +1803,6 @@ int launch_hsmall(vszip_ctx *ctx, const std::vector<RPlane> &pl, int radius, int
 }
 
 #ifdef VSZIP_DEV_VARIANTS  // measured slower than what the default build runs (options.inc)
-// all vertical passes of a small radius in one launch (boxblur_rt_vsmall_kernel); false: the planes do not qualify
-template <typename T>
-bool vsmall_ok(const vszip_ctx *ctx, const std::vector<RPlane> &pl, int radius, int npass) {
-    // Measured (tools/boxblur_radii_probe.py, 1080p, 64 frames per call, against one launch per pass): two passes 93.3 k -> 107.7 k fps (u16), 105 k -> 108 k
-    // (u8); three passes 68 k -> 66.5 k (u16), 79 k -> 65 k (u8) — the chain's rings and registers leave 6 waves a CU at three stages. Hence two passes
-    // only (VSZIP_RT_VSMALL_MAX=3 / 4 for experiments).
-    // End of round 3: OPT-IN (VSZIP_RT_VSMALL=1). The per-pass kernel's LDS ring with its software pipeline (later that round) overtook it: two vertical passes, 1080p, 64 / 16 / 4
-    // frames per call, two launches against this kernel: u8 r = 1 179 k / 191 k / 60 k fps against 156 k / 160 k / 48 k, u16 147 k / 167 k / 68 k against 153 k / 160 k / 49 k; from r = 3 on
-    // this kernel falls to 64 - 105 k (its rings leave few waves a CU) where two launches stay at 137 - 180 k (tools/boxblur_radii_probe.py).
-    if (!ctx->opt.rt_vsmall) return false;
-    const int max_pass = std::min(4, std::max(2, (int)ctx->opt.rt_vsmall_max));
-    if (!std::is_integral<T>::value || sizeof(T) > 2 || npass < 2 || npass > max_pass || radius < 1 || radius > kVsMaxR || ctx->opt.rt_no_vsmall) return false;
-    if ((size_t)npass * (2 * radius + 2) * 1024 > 40 * 1024) return false;  // the rings: four waves a CU at least
-    for (const RPlane &q : pl) {
-        if (!rt_aligned<T>(q) || q.h <= 2 * npass * radius + 2 || q.sstride < ((q.w + 7) / 8) * 8 || q.dstride < ((q.w + 7) / 8) * 8) return false;
-    }
-    return true;
-}
 template <typename T>
 int launch_vsmall(vszip_ctx *ctx, const std::vector<RPlane> &pl, int radius, int npass, bool keep) {
     // (not vszip_for_each_table: a plane's block count depends on the band length, which is chosen from the whole table)
@@ -1871,8 +1844,6 @@ int launch_vsmall(vszip_ctx *ctx, const std::vector<RPlane> &pl, int radius, int
 }
 
 #else
-template <typename T>
-bool vsmall_ok(const vszip_ctx *, const std::vector<RPlane> &, int, int) { return false; }
 template <typename T>
 int launch_vsmall(vszip_ctx *ctx, const std::vector<RPlane> &, int, int, bool) { return vszip_set_error(ctx, VSZIP_ERR_UNSUPPORTED, "boxblur_rt_vsmall_kernel is a development variant"); }
 #endif  // VSZIP_DEV_VARIANTS
@@ -1977,44 +1948,6 @@ int launch_pass(vszip_ctx *ctx, const std::vector<RPlane> &pl, int radius, bool 
         });
 }
 
-// The float chain kernels: 2 ... 5 passes, lines of at least 2 R + 2 samples, rings within one workgroup's LDS.
-constexpr int kFcMaxPass = 5;
-template <typename T>
-bool fchain_ok(const vszip_ctx *ctx, const std::vector<RPlane> &pl, int radius, int npass, bool vertical, int bands = 1) {
-    constexpr bool is_int = std::is_integral<T>::value;
-    if ((is_int ? ctx->opt.rt_no_ichain : ctx->opt.rt_no_fchain) || npass < 2 || npass > kFcMaxPass) return false;
-    if (is_int && (!vertical || sizeof(T) > 2 || radius > 127)) return false;  // integer planes: the vertical chain only (the horizontal passes have boxblur_rt_hsmall_kernel)
-    // 8-bit planes: the per-pass kernel moves 16 samples a lane and wins up to four passes and at larger radii (1080p, 64 frames per call, chain against a launch per pass:
-    // r = 2 x 3 passes -11 %, 13 x 2 -19 %, 2 x 4 even, 3 x 5 +16 %; 16-bit planes: +12 ... +55 % throughout — tools/boxblur_radii_probe.py). VSZIP_RT_ICHAIN_ALL=1: every case (tests).
-    if (is_int && bands < 2 && sizeof(T) == 1 && !(npass >= 5 && radius <= 8) && !ctx->opt.rt_ichain_all) return false;
-    if (is_int && bands < 2 && !ctx->opt.rt_ichain_all) {
-        // Two passes: two launches of the per-pass kernel are as fast (u16, r >= 3: the chain +3 ... 8 % at 64 frames) and do not mind small calls. And the chain is as slow as its
-        // longest column (a wave per 64 columns, ~0.1 us a tick): with fewer waves than SIMDs — a plugin context submits ONE frame per call — the per-pass kernels, which
-        // cut a plane into bands, are several times faster (4 1080p frames, three passes: ~110 us against 3 x 25 us).
-        if (npass < 3) return false;
-        long waves = 0;
-        for (const RPlane &q : pl) waves += (q.w + 63) / 64;
-        if (waves < 900) return false;
-    }
-    if (!is_int && !vertical && !ctx->opt.rt_fchain_all) {
-        // The horizontal chain carries 64 rows a wave and costs what a row's ticks cost however few waves there are; the per-pass kernel (16 rows a wave) is faster on small calls:
-        // 4K YUV420PS, 3 passes of r = 5, 1 / 2 / 4 frames per call: chain 2.5 k / 5.0 k / 9.7 k fps, a launch per pass 3.0 k / 5.7 k / 9.2 k. (The vertical chain wins from one frame on.)
-        long rows = 0;
-        for (const RPlane &q : pl) rows += q.h;
-        if (rows < 12000) return false;
-    }
-    const size_t esz = sizeof(typename FcArith<T>::E);
-    const size_t lds = vertical ? ((size_t)npass * (2 * radius + 3) + kFcPf + 8) * 64 * esz : (size_t)npass * (2 * radius + 3) * kFcRB * sizeof(float);
-    if (lds > (vertical ? 48 : 30) * 1024) return false;  // (the horizontal kernel also holds two 64 x 64 tiles)
-    for (const RPlane &q : pl) {
-        if ((vertical ? q.h : q.w) < 2 * radius + 2) return false;
-        if (vertical) {  // rows go four samples a lane
-            if (!rt_aligned<T>(q, 4 * sizeof(T) - 1) || q.sstride < ((q.w + 3) & ~3) || q.w < 4) return false;
-        }
-    }
-    return true;
-}
-
 template <typename T>
 int launch_fchain(vszip_ctx *ctx, const std::vector<RPlane> &pl, int radius, int npass, bool vertical, bool keep) {
     RParams prm = rt_table(radius, keep);
@@ -2025,8 +1958,7 @@ int launch_fchain(vszip_ctx *ctx, const std::vector<RPlane> &pl, int radius, int
             return vertical ? (d.w + 63) / 64 : (d.h + kFcRB - 1) / kFcRB;
         },
         [&](const RParams &prm, int blocks, int) -> int {
-            const int D = 2 * radius + 3;
-            const size_t lds = vertical ? ((size_t)npass * D + kFcPf + 8) * 64 * sizeof(typename FcArith<T>::E) : (size_t)npass * D * kFcRB * sizeof(float);
+            const size_t lds = rt_plan::chain_lds_bytes({std::is_integral<T>::value, (int)sizeof(T)}, radius, npass, vertical);
 #define VSZIP_FC_LAUNCH(PP)                                                                                                        \
     case PP:                                                                                                                       \
         if (vertical) {                                                                                                            \
@@ -2047,70 +1979,7 @@ int launch_fchain(vszip_ctx *ctx, const std::vector<RPlane> &pl, int radius, int
         });
 }
 
-// The banded integer vertical chain (boxblur_rt_ichain_kernel): the planes qualify when the unbanded chain does, are tall enough for the mirror
-// extension (P (R + 1) + 1 rows) and for at least two bands of 2 P (2R + 1) rows — below that a band's warm-up is more than its rows.
-// How many bands: a cost model fitted to tools/rt_band_sweep.py (gpurun_out/r4_rt_band_sweep.txt: 12 workloads x 8 band counts). A wave's time is its ticks — the band's rows
-// + P (2R + 1) warm-up + P (R + 1) drain — times the tick's latency, which grows with the waves sharing a SIMD (about +36 % per extra wave: LDS hand-overs and the
-// loop-carried sums leave gaps that a second wave fills only partly); the rings' LDS bounds the resident waves (five stages of r = 13: 23.7 KB a wave, six waves a CU),
-// beyond which waves queue. T(nb) = max(longest wave, all wave-ticks / resident waves) x slow(waves per SIMD); the band count with the smallest T wins, 1 = no bands
-// (the callers then choose between the whole-column chain and a launch per pass as before).
-template <typename T>
-int ichain_band_rows(const vszip_ctx *ctx, const std::vector<RPlane> &pl, int radius, int npass) {
-    if (!std::is_integral<T>::value || sizeof(T) > 2 || ctx->opt.rt_no_banded) return 0;
-    int maxh = 0, minh = 1 << 30;
-    for (const RPlane &q : pl) {
-        maxh = std::max(maxh, q.h);
-        minh = std::min(minh, q.h);
-    }
-    if (minh < npass * (radius + 1) + 1) return 0;  // (the mirror extension reflects once)
-    if (ctx->opt.rt_ichain_bands > 0) {  // (tests and sweeps: any band count)
-        const int nb = std::min(ctx->opt.rt_ichain_bands, std::max(1, maxh / 8));
-        return nb < 2 ? 0 : (maxh + nb - 1) / nb;
-    }
-    const int warm = npass * (2 * radius + 1), drain = npass * (radius + 1);
-    const size_t lds = ((size_t)npass * (2 * radius + 3) + kFcPf + 8) * 64 * sizeof(uint16_t);
-    const double cap = 256.0 * std::min<double>(16.0, std::floor(160.0 * 1024 / (double)lds));
-    auto cost = [&](int nb) {
-        const int br = (maxh + nb - 1) / nb;
-        double total = 0, waves = 0, longest = 0;
-        for (const RPlane &q : pl) {
-            const int ncg = (q.w + 63) / 64;
-            if (nb == 1) {  // whole columns: the generic ticks at both ends cost about three fast ones
-                const double t = q.h + drain + 2.0 * warm;
-                total += ncg * t;
-                waves += ncg;
-                longest = std::max(longest, t);
-                continue;
-            }
-            const int nbp = (q.h + br - 1) / br;
-            for (int b = 0; b < nbp; ++b) {
-                const double t = std::min(br, q.h - b * br) + warm + drain;
-                total += ncg * t;
-                longest = std::max(longest, t);
-            }
-            waves += (double)ncg * nbp;
-        }
-        // (a grid search over the five constants against the sweep's 12 x 9 measurements: the model's pick is the measured optimum on nine workloads and
-        // within 4 % of it on the other three — profiles/r04_rt_band_sweep.txt, tools/rt_band_fit.py)
-        const double conc = std::min(waves, cap), w = conc / 1024.0;
-        const double slow = 1.0 + 0.2 * std::max(0.0, w - 0.75);
-        double t = std::max(longest, total / conc) * slow;
-        if (waves > conc) t += 0.3 * longest * slow;  // queued waves: the last ones run beside idle slots
-        return t + (nb > 1 ? 1.0 * drain : 0.0);      // (+ the launch that fills the table of constants)
-    };
-    int best_nb = 1;
-    double best = cost(1);
-    for (int nb : {2, 3, 4, 5, 6, 8, 10, 12, 16, 20, 24, 32}) {
-        if ((maxh + nb - 1) / nb < 32) break;
-        const double c = cost(nb);
-        if (c < best) {
-            best = c;
-            best_nb = nb;
-        }
-    }
-    return best_nb < 2 ? 0 : (maxh + best_nb - 1) / best_nb;
-}
-template <typename T>
+// The banded integer vertical chain (boxblur_rt_ichain_kernel) in bands of band_rows rows (rt_plan::ichain_band_rows); kk_tab: room for ichain_table_bytes.
 size_t ichain_table_bytes(const std::vector<RPlane> &pl) {
     size_t e = 0;
     for (const RPlane &q : pl) e += (size_t)((q.w + 63) & ~63) * kFcMaxPass;
@@ -2118,293 +1987,257 @@ size_t ichain_table_bytes(const std::vector<RPlane> &pl) {
 }
 template <typename T>
 int launch_ichain_banded(vszip_ctx *ctx, const std::vector<RPlane> &pl, int radius, int npass, bool keep, int band_rows, uint32_t *kk_tab) {
-    if constexpr (std::is_integral<T>::value && sizeof(T) <= 2) {
-        size_t kk_off = 0;
-        RParams prm = rt_table(radius, keep);
-        return vszip_for_each_table(
-            ctx, prm, (int)pl.size(),
-            [&](RPlane &d, int i) -> int {
-                d = pl[i];
-                const int ncg = (d.w + 63) / 64;
-                d.aux = (int)kk_off;
-                kk_off += (size_t)ncg * 64 * kFcMaxPass;
-                return ncg * ((d.h + band_rows - 1) / band_rows);
-            },
-            [&](const RParams &prm, int blocks, int) -> int {
-                RParams pe0 = prm;  // the launch that fills the table of constants: one workgroup per column group
-                int blocks0 = 0;
-                for (int i = 0; i < pe0.nplanes; ++i) {
-                    pe0.p[i].block0 = blocks0;
-                    blocks0 += (pe0.p[i].w + 63) / 64;
-                }
-                const int D = 2 * radius + 3;
-                const size_t lds = ((size_t)npass * D + kFcPf + 8) * 64 * sizeof(uint16_t);
+    size_t kk_off = 0;
+    RParams prm = rt_table(radius, keep);
+    return vszip_for_each_table(
+        ctx, prm, (int)pl.size(),
+        [&](RPlane &d, int i) -> int {
+            d = pl[i];
+            const int ncg = (d.w + 63) / 64;
+            d.aux = (int)kk_off;
+            kk_off += (size_t)ncg * 64 * kFcMaxPass;
+            return ncg * ((d.h + band_rows - 1) / band_rows);
+        },
+        [&](const RParams &prm, int blocks, int) -> int {
+            RParams pe0 = prm;  // the launch that fills the table of constants: one workgroup per column group
+            int blocks0 = 0;
+            for (int i = 0; i < pe0.nplanes; ++i) {
+                pe0.p[i].block0 = blocks0;
+                blocks0 += (pe0.p[i].w + 63) / 64;
+            }
+            const size_t lds = rt_plan::chain_lds_bytes({true, (int)sizeof(T)}, radius, npass, true);
 #define VSZIP_IC_LAUNCH(PP)                                                                                                              \
     case PP:                                                                                                                             \
         hipLaunchKernelGGL((boxblur_rt_ichain_kernel<T, PP, 1>), dim3(blocks0), dim3(64), lds, ctx->stream, pe0, kk_tab, band_rows);     \
         hipLaunchKernelGGL((boxblur_rt_ichain_kernel<T, PP, 2>), dim3(blocks), dim3(64), lds, ctx->stream, prm, kk_tab, band_rows);      \
         break;
-                switch (npass) {
-                    VSZIP_IC_LAUNCH(2)
-                    VSZIP_IC_LAUNCH(3)
-                    VSZIP_IC_LAUNCH(4)
-                    VSZIP_IC_LAUNCH(5)
-                }
+            switch (npass) {
+                VSZIP_IC_LAUNCH(2)
+                VSZIP_IC_LAUNCH(3)
+                VSZIP_IC_LAUNCH(4)
+                VSZIP_IC_LAUNCH(5)
+            }
 #undef VSZIP_IC_LAUNCH
+            return VSZIP_OK;
+        });
+}
+
+#ifdef VSZIP_DEV_VARIANTS  // measured slower than what the default build runs (options.inc)
+// Integer planes with >= 2 passes on an axis, OPT-IN (VSZIP_RT_FUSED=1): the fused kernel keeps a row in registers across that
+// axis's passes (horizontal directly; vertical, from 3 passes on, between two transposes: four HBM round trips for any 5 + 5
+// instead of ten). Bit-exact (tests/test_gpu_boxblur.py::test_rt_fused_multipass_equals_per_pass) — and measured SLOWER than
+// the per-pass kernels, which is why it is not the default: 5 fused passes of r = 13 on 16 1080p YUV420P16 frames take 511 us
+// against 5 x 65 us separately. The per-pass kernels are not HBM-bound but issue-bound (about 12 instructions per sample and
+// pass at 4.3 TB/s effective); a kernel that keeps the row on chip needs about 19 (the whole row's prefix has to go through
+// LDS with three barriers per pass), so saving the round trips buys nothing. The README's 5 + 5-pass benchmark therefore stays
+// at ten round trips (profiles/r03_notes.md).
+// *taken: the fused kernels run these planes (then the result is the call's); else nothing was done.
+template <typename T>
+int run_rt_fused(vszip_ctx *ctx, const vszip_plane *planes, int nplanes, int hradius, int hpasses, int vradius, int vpasses, bool *taken) {
+    const bool hb = hradius > 0 && hpasses > 0, vb = vradius > 0 && vpasses > 0;
+    const int total = (hb ? hpasses : 0) + (vb ? vpasses : 0);
+    bool ok = ctx->opt.rt_fused && total > 1;
+    const bool fuse_h = hb && hpasses >= 2, fuse_v = vb && vpasses >= 3;
+    ok = ok && (fuse_h || fuse_v);
+    for (int i = 0; i < nplanes && ok; ++i) {
+        const vszip_plane &q = planes[i];
+        ok = (((reinterpret_cast<uintptr_t>(q.src) | reinterpret_cast<uintptr_t>(q.dst) | (uintptr_t)((size_t)q.src_stride * sizeof(T)) | (uintptr_t)((size_t)q.dst_stride * sizeof(T))) & 15) == 0) &&
+             (size_t)q.src_stride >= (size_t)((q.w + RtVec<T>::V - 1) / RtVec<T>::V) * RtVec<T>::V;
+        if (fuse_h) ok = ok && q.w <= kHmMaxW && 2 * hradius < q.w && hradius <= kHmMaxR;
+        if (fuse_v) ok = ok && q.h <= kHmMaxW && 2 * vradius < q.h && vradius <= kHmMaxR;
+    }
+    *taken = ok;
+    if (!ok) return VSZIP_OK;
+    // scratch: two buffers that hold a plane set in either orientation (rows padded to 64 samples)
+    std::vector<size_t> poff(nplanes);
+    size_t pe = 0;
+    for (int i = 0; i < nplanes; ++i) {
+        poff[i] = pe;
+        pe += std::max((size_t)((planes[i].w + 63) & ~63) * planes[i].h, (size_t)((planes[i].h + 63) & ~63) * planes[i].w);
+    }
+    int rc = vszip_ensure_scratch(ctx, 2 * pe * sizeof(T) + 256);
+    if (rc != VSZIP_OK) return rc;
+    T *buf[2] = {static_cast<T *>(ctx->scratch), static_cast<T *>(ctx->scratch) + pe};
+    struct Cur { const void *ptr; int stride, w, h; };
+    std::vector<Cur> cur(nplanes);
+    for (int i = 0; i < nplanes; ++i) cur[i] = Cur{planes[i].src, (int)planes[i].src_stride, planes[i].w, planes[i].h};
+    int which = 0;
+    // one step over all planes: kind 0 = fused passes along the rows, 1 = transpose; `to_dst`: into the caller's planes
+    auto step = [&](int kind, int radius, int npass, bool to_dst) -> int {
+        RParams prm = rt_table(radius, !to_dst);
+        const int st = vszip_for_each_table(
+            ctx, prm, nplanes,
+            [&](RPlane &r, int gi) -> int {
+                r.src = cur[gi].ptr;
+                r.sstride = cur[gi].stride;
+                r.w = cur[gi].w;
+                r.h = cur[gi].h;
+                const int ow = kind == 1 ? cur[gi].h : cur[gi].w;
+                if (to_dst) {
+                    r.dst = planes[gi].dst;
+                    r.dstride = (int)planes[gi].dst_stride;
+                } else {
+                    r.dst = buf[which] + poff[gi];
+                    r.dstride = (ow + 63) & ~63;
+                }
+                return kind == 1 ? ((r.w + 63) / 64) * ((r.h + 63) / 64) : r.h;
+            },
+            [&](const RParams &prm, int blocks, int first) -> int {
+                if (kind == 1)
+                    hipLaunchKernelGGL((rt_transpose_kernel<T>), dim3(blocks), dim3(256), 0, ctx->stream, prm);
+                else
+                    hipLaunchKernelGGL((boxblur_rt_hmulti_kernel<T>), dim3(blocks), dim3(kHmNT), 0, ctx->stream, prm, npass);
+                for (int i = 0; i < prm.nplanes; ++i) {
+                    const RPlane &r = prm.p[i];
+                    cur[first + i] = kind == 1 ? Cur{r.dst, r.dstride, r.h, r.w} : Cur{r.dst, r.dstride, r.w, r.h};
+                }
                 return VSZIP_OK;
             });
+        if (st != VSZIP_OK) return st;
+        which ^= 1;
+        return VSZIP_OK;
+    };
+    // the per-pass kernels on the current planes (an axis the fused kernel does not take), into scratch or the caller's planes
+    auto per_pass = [&](int radius, int npass, bool vertical, bool last_axis) -> int {
+        for (int p = 0; p < npass; ++p) {
+            const bool to_dst = last_axis && p == npass - 1;
+            std::vector<RPlane> v(nplanes);
+            for (int i = 0; i < nplanes; ++i) {
+                v[i].src = cur[i].ptr;
+                v[i].sstride = cur[i].stride;
+                v[i].w = cur[i].w;
+                v[i].h = cur[i].h;
+                v[i].dst = to_dst ? planes[i].dst : static_cast<void *>(buf[which] + poff[i]);
+                v[i].dstride = to_dst ? (int)planes[i].dst_stride : ((cur[i].w + 63) & ~63);
+            }
+            const int prc = launch_pass<T>(ctx, v, radius, vertical, !to_dst);
+            if (prc != VSZIP_OK) return prc;
+            for (int i = 0; i < nplanes; ++i) cur[i] = Cur{v[i].dst, v[i].dstride, v[i].w, v[i].h};
+            which ^= 1;
+        }
+        return VSZIP_OK;
+    };
+    if (hb) {
+        rc = fuse_h ? step(0, hradius, hpasses, !vb) : per_pass(hradius, hpasses, false, !vb);
+        if (rc != VSZIP_OK) return rc;
+    }
+    if (vb) {
+        if (fuse_v) {
+            if ((rc = step(1, 0, 0, false)) != VSZIP_OK) return rc;
+            if ((rc = step(0, vradius, vpasses, false)) != VSZIP_OK) return rc;
+            if ((rc = step(1, 0, 0, true)) != VSZIP_OK) return rc;
+        } else if ((rc = per_pass(vradius, vpasses, true, true)) != VSZIP_OK) {
+            return rc;
+        }
+    }
+    return VSZIP_OK;
+}
+#endif  // VSZIP_DEV_VARIANTS
+
+inline rt_plan::Opts rt_plan_opts(const vszip_options &o) {
+    rt_plan::Opts r;
+    r.rt_no_hsmall = o.rt_no_hsmall, r.rt_no_ichain = o.rt_no_ichain, r.rt_no_fchain = o.rt_no_fchain, r.rt_ichain_all = o.rt_ichain_all, r.rt_fchain_all = o.rt_fchain_all;
+    r.rt_no_banded = o.rt_no_banded, r.rt_ichain_bands = o.rt_ichain_bands;
+    r.rt_vsmall = o.rt_vsmall, r.rt_vsmall_max = o.rt_vsmall_max, r.rt_no_vsmall = o.rt_no_vsmall;
+    return r;
+}
+
+// one step of the plan; pl: the step's sources and destinations. A float plan holds Pass and FloatChain only, an integer plan everything but FloatChain.
+template <typename T>
+int run_step(vszip_ctx *ctx, const std::vector<RPlane> &pl, const rt_plan::Step &st, uint32_t *kk_tab) {
+    using rt_plan::Kind;
+    const bool keep = !st.to_dst;
+    if (st.kind == Kind::Pass) return launch_pass<T>(ctx, pl, st.radius, st.vertical, keep);
+    if constexpr (!std::is_integral<T>::value) {
+        return launch_fchain<T>(ctx, pl, st.radius, st.span, st.vertical, keep);
     } else {
-        return VSZIP_ERR_ARG;
+        switch (st.kind) {
+            case Kind::IntChainBanded: return launch_ichain_banded<T>(ctx, pl, st.radius, st.span, keep, st.band_rows, kk_tab);
+            case Kind::IntChainWhole: return launch_fchain<T>(ctx, pl, st.radius, st.span, true, keep);
+            case Kind::HSmall: return launch_hsmall<T>(ctx, pl, st.radius, st.span, keep);
+            case Kind::VSmall: return launch_vsmall<T>(ctx, pl, st.radius, st.span, keep);
+            default: __builtin_unreachable();
+        }
     }
 }
 
+// the caller's planes as the planner sees them
+template <typename T>
+std::vector<rt_plan::Plane> rt_plan_planes(const vszip_plane *planes, int nplanes) {
+    std::vector<rt_plan::Plane> geo(nplanes);
+    for (int i = 0; i < nplanes; ++i) {
+        const vszip_plane &q = planes[i];
+        geo[i] = rt_plan::Plane{q.w, q.h, (int)q.src_stride, (int)q.dst_stride,
+                                (unsigned)((reinterpret_cast<uintptr_t>(q.src) | (uintptr_t)((size_t)q.src_stride * sizeof(T))) & 15),
+                                (unsigned)((reinterpret_cast<uintptr_t>(q.dst) | (uintptr_t)((size_t)q.dst_stride * sizeof(T))) & 15)};
+    }
+    return geo;
+}
+
+// boxblur.zig:85-112: hpasses horizontal passes, then vpasses vertical passes — planned by rt_plan::rt_plan, executed here.
+// Groups: the planes go through ALL passes in groups small enough that a pass's output is still in the Infinity
+// Cache (256 MiB, memory side) when the next pass reads it — a line stays resident while everything touched between its two
+// uses fits (MI355X_MICROARCH.md, Infinity Cache): about three group sizes here, so groups of <= 48 MB. HBM then sees the
+// first read and the last write; the passes in between run cache to cache (their stores drop the nt hint). One pass, or
+// VSZIP_RT_GROUP_MB=0: one group.
+// (measured, round 3: 4K YUV420P16 3 + 3 passes of r = 5, groups of 24 / 48 / 96 MB: 8.4 k / 12.8 k / 13.6 k fps against 13.5 k in one
+// group — the passes are not HBM-bound enough for residency to beat the smaller launches; the default is ONE group)
 template <typename T>
 int run_rt(vszip_ctx *ctx, const vszip_plane *planes, int nplanes, int hradius, int hpasses, int vradius, int vpasses) {
-    // boxblur.zig:85-112: hpasses horizontal passes, then vpasses vertical passes
-    const bool hb = hradius > 0 && hpasses > 0, vb = vradius > 0 && vpasses > 0;
-    const int total = (hb ? hpasses : 0) + (vb ? vpasses : 0);
-    size_t elems = 0;
-    std::vector<size_t> off(nplanes);
-    for (int i = 0; i < nplanes; ++i) {
-        off[i] = elems;
-        elems += (size_t)((planes[i].w + 63) & ~63) * planes[i].h;
-    }
-#ifdef VSZIP_DEV_VARIANTS  // measured slower than what the default build runs (options.inc)
-    // Integer planes with >= 2 passes on an axis, OPT-IN (VSZIP_RT_FUSED=1): the fused kernel keeps a row in registers across that
-    // axis's passes (horizontal directly; vertical, from 3 passes on, between two transposes: four HBM round trips for any 5 + 5
-    // instead of ten). Bit-exact (tests/test_gpu_boxblur.py::test_rt_fused_multipass_equals_per_pass) — and measured SLOWER than
-    // the per-pass kernels, which is why it is not the default: 5 fused passes of r = 13 on 16 1080p YUV420P16 frames take 511 us
-    // against 5 x 65 us separately. The per-pass kernels are not HBM-bound but issue-bound (about 12 instructions per sample and
-    // pass at 4.3 TB/s effective); a kernel that keeps the row on chip needs about 19 (the whole row's prefix has to go through
-    // LDS with three barriers per pass), so saving the round trips buys nothing. The README's 5 + 5-pass benchmark therefore stays
-    // at ten round trips (profiles/r03_notes.md).
+#ifdef VSZIP_DEV_VARIANTS
     if constexpr (std::is_integral<T>::value) {
-        bool ok = ctx->opt.rt_fused && total > 1;
-        const bool fuse_h = hb && hpasses >= 2, fuse_v = vb && vpasses >= 3;
-        ok = ok && (fuse_h || fuse_v);
-        for (int i = 0; i < nplanes && ok; ++i) {
-            const vszip_plane &q = planes[i];
-            ok = (((reinterpret_cast<uintptr_t>(q.src) | reinterpret_cast<uintptr_t>(q.dst) | (uintptr_t)((size_t)q.src_stride * sizeof(T)) | (uintptr_t)((size_t)q.dst_stride * sizeof(T))) & 15) == 0) &&
-                 (size_t)q.src_stride >= (size_t)((q.w + RtVec<T>::V - 1) / RtVec<T>::V) * RtVec<T>::V;
-            if (fuse_h) ok = ok && q.w <= kHmMaxW && 2 * hradius < q.w && hradius <= kHmMaxR;
-            if (fuse_v) ok = ok && q.h <= kHmMaxW && 2 * vradius < q.h && vradius <= kHmMaxR;
-        }
-        if (ok) {
-            // scratch: two buffers that hold a plane set in either orientation (rows padded to 64 samples)
-            std::vector<size_t> poff(nplanes);
-            size_t pe = 0;
-            for (int i = 0; i < nplanes; ++i) {
-                poff[i] = pe;
-                pe += std::max((size_t)((planes[i].w + 63) & ~63) * planes[i].h, (size_t)((planes[i].h + 63) & ~63) * planes[i].w);
-            }
-            int rc = vszip_ensure_scratch(ctx, 2 * pe * sizeof(T) + 256);
-            if (rc != VSZIP_OK) return rc;
-            T *buf[2] = {static_cast<T *>(ctx->scratch), static_cast<T *>(ctx->scratch) + pe};
-            struct Cur { const void *ptr; int stride, w, h; };
-            std::vector<Cur> cur(nplanes);
-            for (int i = 0; i < nplanes; ++i) cur[i] = Cur{planes[i].src, (int)planes[i].src_stride, planes[i].w, planes[i].h};
-            int which = 0;
-            // one step over all planes: kind 0 = fused passes along the rows, 1 = transpose; `to_dst`: into the caller's planes
-            auto step = [&](int kind, int radius, int npass, bool to_dst) -> int {
-                RParams prm = rt_table(radius, !to_dst);
-                const int st = vszip_for_each_table(
-                    ctx, prm, nplanes,
-                    [&](RPlane &r, int gi) -> int {
-                        r.src = cur[gi].ptr;
-                        r.sstride = cur[gi].stride;
-                        r.w = cur[gi].w;
-                        r.h = cur[gi].h;
-                        const int ow = kind == 1 ? cur[gi].h : cur[gi].w;
-                        if (to_dst) {
-                            r.dst = planes[gi].dst;
-                            r.dstride = (int)planes[gi].dst_stride;
-                        } else {
-                            r.dst = buf[which] + poff[gi];
-                            r.dstride = (ow + 63) & ~63;
-                        }
-                        return kind == 1 ? ((r.w + 63) / 64) * ((r.h + 63) / 64) : r.h;
-                    },
-                    [&](const RParams &prm, int blocks, int first) -> int {
-                        if (kind == 1)
-                            hipLaunchKernelGGL((rt_transpose_kernel<T>), dim3(blocks), dim3(256), 0, ctx->stream, prm);
-                        else
-                            hipLaunchKernelGGL((boxblur_rt_hmulti_kernel<T>), dim3(blocks), dim3(kHmNT), 0, ctx->stream, prm, npass);
-                        for (int i = 0; i < prm.nplanes; ++i) {
-                            const RPlane &r = prm.p[i];
-                            cur[first + i] = kind == 1 ? Cur{r.dst, r.dstride, r.h, r.w} : Cur{r.dst, r.dstride, r.w, r.h};
-                        }
-                        return VSZIP_OK;
-                    });
-                if (st != VSZIP_OK) return st;
-                which ^= 1;
-                return VSZIP_OK;
-            };
-            // the per-pass kernels on the current planes (an axis the fused kernel does not take), into scratch or the caller's planes
-            auto per_pass = [&](int radius, int npass, bool vertical, bool last_axis) -> int {
-                for (int p = 0; p < npass; ++p) {
-                    const bool to_dst = last_axis && p == npass - 1;
-                    std::vector<RPlane> v(nplanes);
-                    for (int i = 0; i < nplanes; ++i) {
-                        v[i].src = cur[i].ptr;
-                        v[i].sstride = cur[i].stride;
-                        v[i].w = cur[i].w;
-                        v[i].h = cur[i].h;
-                        v[i].dst = to_dst ? planes[i].dst : static_cast<void *>(buf[which] + poff[i]);
-                        v[i].dstride = to_dst ? (int)planes[i].dst_stride : ((cur[i].w + 63) & ~63);
-                    }
-                    const int prc = launch_pass<T>(ctx, v, radius, vertical, !to_dst);
-                    if (prc != VSZIP_OK) return prc;
-                    for (int i = 0; i < nplanes; ++i) cur[i] = Cur{v[i].dst, v[i].dstride, v[i].w, v[i].h};
-                    which ^= 1;
-                }
-                return VSZIP_OK;
-            };
-            if (hb) {
-                rc = fuse_h ? step(0, hradius, hpasses, !vb) : per_pass(hradius, hpasses, false, !vb);
-                if (rc != VSZIP_OK) return rc;
-            }
-            if (vb) {
-                if (fuse_v) {
-                    if ((rc = step(1, 0, 0, false)) != VSZIP_OK) return rc;
-                    if ((rc = step(0, vradius, vpasses, false)) != VSZIP_OK) return rc;
-                    if ((rc = step(1, 0, 0, true)) != VSZIP_OK) return rc;
-                } else if ((rc = per_pass(vradius, vpasses, true, true)) != VSZIP_OK) {
-                    return rc;
-                }
-            }
-            return VSZIP_OK;
-        }
+        bool taken = false;
+        const int rc = run_rt_fused<T>(ctx, planes, nplanes, hradius, hpasses, vradius, vpasses, &taken);
+        if (taken) return rc;
     }
-#endif  // VSZIP_DEV_VARIANTS
-    // Several passes: the planes go through ALL passes in groups small enough that a pass's output is still in the Infinity
-    // Cache (256 MiB, memory side) when the next pass reads it — a line stays resident while everything touched between its two
-    // uses fits (MI355X_MICROARCH.md, Infinity Cache): about three group sizes here, so groups of <= 48 MB. HBM then sees the
-    // first read and the last write; the passes in between run cache to cache (their stores drop the nt hint). One pass, or
-    // VSZIP_RT_GROUP_MB=0: one group.
-    // (measured, round 3: 4K YUV420P16 3 + 3 passes of r = 5, groups of 24 / 48 / 96 MB: 8.4 k / 12.8 k / 13.6 k fps against 13.5 k in one
-    // group — the passes are not HBM-bound enough for residency to beat the smaller launches; the default is ONE group)
-    size_t group_bytes = ~(size_t)0;
+#endif
+    const rt_plan::Elem elem{std::is_integral<T>::value, (int)sizeof(T)};
+    const rt_plan::Opts opts = rt_plan_opts(ctx->opt);
+    const std::vector<rt_plan::Plane> geo = rt_plan_planes<T>(planes, nplanes);
+    size_t group_bytes = ~(size_t)0;  // (one group; every group is planned on its own)
     if (ctx->opt.rt_group_mb > 0) group_bytes = (size_t)ctx->opt.rt_group_mb << 20;  // (-DVSZIP_DEV_VARIANTS)
-    int g0 = 0;
-    while (g0 < nplanes) {
-        int g1 = g0;
-        size_t bytes = 0, elems_g = 0;
-        while (g1 < nplanes && (g1 == g0 || bytes + (size_t)planes[g1].w * planes[g1].h * sizeof(T) <= group_bytes)) {
-            bytes += (size_t)planes[g1].w * planes[g1].h * sizeof(T);
-            elems_g += (size_t)((planes[g1].w + 63) & ~63) * planes[g1].h;
-            ++g1;
-        }
+    for (int g0 = 0, g1; g0 < nplanes; g0 = g1) {
+        size_t bytes = 0;
+        for (g1 = g0; g1 < nplanes && (g1 == g0 || bytes + (size_t)planes[g1].w * planes[g1].h * sizeof(T) <= group_bytes); ++g1) bytes += (size_t)planes[g1].w * planes[g1].h * sizeof(T);
         const int ng = g1 - g0;
-        T *scratch[2] = {nullptr, nullptr};
-        uint32_t *kk_tab = nullptr;  // the banded integer chain's per-column constants
-        std::vector<size_t> goff(ng);
-        {
-            size_t e = 0;
-            for (int i = 0; i < ng; ++i) {
-                goff[i] = e;
-                e += (size_t)((planes[g0 + i].w + 63) & ~63) * planes[g0 + i].h;
-            }
-        }
-        if (total > 1) {
-            // (grow-only scratch sized for the largest group seen; every group reuses the same two buffers)
-            const size_t planes_bytes = (2 * elems_g * sizeof(T) + 255) & ~(size_t)255;
-            size_t tab_bytes = 0;
-            if (std::is_integral<T>::value && vb && vpasses >= 2)
-                for (int i = 0; i < ng; ++i) tab_bytes += (size_t)((planes[g0 + i].w + 63) & ~63) * kFcMaxPass * sizeof(uint32_t);
-            int rc = vszip_ensure_scratch(ctx, planes_bytes + tab_bytes + 256);
-            if (rc != VSZIP_OK) return rc;
-            scratch[0] = static_cast<T *>(ctx->scratch);
-            scratch[1] = scratch[0] + elems_g;
-            kk_tab = reinterpret_cast<uint32_t *>(static_cast<char *>(ctx->scratch) + planes_bytes);
-        }
+        const std::vector<rt_plan::Step> plan = rt_plan::rt_plan(geo.data() + g0, ng, elem, opts, hradius, hpasses, vradius, vpasses);
         std::vector<RPlane> cur(ng);
+        std::vector<size_t> goff(ng);  // plane i within a scratch plane set
+        size_t elems = 0;
         for (int i = 0; i < ng; ++i) {
             cur[i].src = planes[g0 + i].src;
             cur[i].sstride = (int)planes[g0 + i].src_stride;
             cur[i].w = planes[g0 + i].w;
             cur[i].h = planes[g0 + i].h;
+            goff[i] = elems;
+            elems += (size_t)rt_plan::scratch_pitch(cur[i].w) * cur[i].h;
         }
-        int which = 0;
-        for (int p = 0; p < total; ++p) {
-            const bool vertical = p >= (hb ? hpasses : 0);
-            // every horizontal pass of a small radius at once (round 3): the step then stands for hpasses passes
-            int span = 1;
-            if constexpr (!std::is_integral<T>::value) {
-                // float: what is left of this axis's passes in chains of up to kFcMaxPass stages (6 = 3 + 3 rather than 5 + 1: a lone pass is a launch of its own)
-                const int rem = vertical ? total - p : hpasses - p;
-                if (rem >= 2) span = rem <= kFcMaxPass ? rem : (rem - kFcMaxPass == 1 ? kFcMaxPass - 1 : kFcMaxPass);
-            } else if constexpr (sizeof(T) <= 2) {
-                if (p == 0 && hb && hpasses >= 2) span = hpasses;
-                if (vertical) {
-                    // What is left of the vertical passes, in chains of nearly equal length. A chain of P stages costs every row band P (3 R + 2) rows of
-                    // warm-up and drain and P (2 R + 3) ring rows of LDS, so short planes take shorter chains and pay another trip through memory instead:
-                    // at most a quarter of the shortest plane's rows may be warm-up (r = 13 on 1080p 4:2:0, 540-row chroma: 5 passes as 3 + 2 - 292 us
-                    // against 343 for one chain of 5 on 32 frames, 4 as 2 + 2 - 218 against 234; 4K keeps its chain of 5: 246 against 289;
-                    // tools/rt_pass_scaling.py)
-                    const int rem = total - p;
-                    int minh = 1 << 30;
-                    for (int i = 0; i < ng; ++i) minh = std::min(minh, cur[i].h);
-                    const int pmax = std::max(2, std::min(kFcMaxPass, minh / (4 * (3 * vradius + 2))));
-                    if (rem >= 2) {
-                        const int nchains = (rem + pmax - 1) / pmax;
-                        span = (rem + nchains - 1) / nchains;
-                    }
-                }
-            }
-            const bool last = p + span - 1 == total - 1;
+        // scratch (grow-only, sized for the largest group seen; every group reuses it): two plane sets when a step's output is another's input,
+        // then the banded chain's per-column constants
+        bool banded = false;
+        for (const rt_plan::Step &st : plan) banded = banded || st.kind == rt_plan::Kind::IntChainBanded;
+        const size_t planes_bytes = plan.size() > 1 ? (2 * elems * sizeof(T) + 255) & ~(size_t)255 : 0;
+        T *scratch[2] = {nullptr, nullptr};
+        uint32_t *kk_tab = nullptr;
+        if (planes_bytes || banded) {
+            const int rc = vszip_ensure_scratch(ctx, planes_bytes + (banded ? ichain_table_bytes(cur) : 0) + 256);
+            if (rc != VSZIP_OK) return rc;
+            scratch[0] = static_cast<T *>(ctx->scratch);
+            scratch[1] = scratch[0] + elems;
+            kk_tab = reinterpret_cast<uint32_t *>(static_cast<char *>(ctx->scratch) + planes_bytes);
+        }
+        for (const rt_plan::Step &st : plan) {
             for (int i = 0; i < ng; ++i) {
-                if (last) {
-                    cur[i].dst = planes[g0 + i].dst;
-                    cur[i].dstride = (int)planes[g0 + i].dst_stride;
-                } else {
-                    cur[i].dst = scratch[which] + goff[i];
-                    cur[i].dstride = (planes[g0 + i].w + 63) & ~63;
-                }
+                cur[i].dst = st.to_dst ? planes[g0 + i].dst : static_cast<void *>(scratch[st.scratch] + goff[i]);
+                cur[i].dstride = st.to_dst ? (int)planes[g0 + i].dst_stride : rt_plan::scratch_pitch(cur[i].w);
             }
-            int rc;
-            if (!std::is_integral<T>::value && span > 1 && fchain_ok<T>(ctx, cur, vertical ? vradius : hradius, span, vertical)) {
-                if constexpr (!std::is_integral<T>::value) rc = launch_fchain<T>(ctx, cur, vertical ? vradius : hradius, span, vertical, !last);
-                else rc = VSZIP_ERR_ARG;
-                p += span - 1;
-            } else if (const int br = (std::is_integral<T>::value && span > 1 && vertical && kk_tab && !vsmall_ok<T>(ctx, cur, vradius, span)) ? ichain_band_rows<T>(ctx, cur, vradius, span) : 0;
-                       br > 0 && fchain_ok<T>(ctx, cur, vradius, span, true, (cur[0].h + br - 1) / br)) {
-                // integer planes: the chain in bands of rows (exact under any segmentation: see boxblur_rt_ichain_kernel)
-                rc = launch_ichain_banded<T>(ctx, cur, vradius, span, !last, br, kk_tab);
-                p += span - 1;
-            } else if (std::is_integral<T>::value && span > 1 && vertical && !vsmall_ok<T>(ctx, cur, vradius, span) && fchain_ok<T>(ctx, cur, vradius, span, true)) {
-                // integer planes, vertical passes the two-stage small-radius kernel does not take: the pass chain (one column a lane, the stages' rings in LDS)
-                if constexpr (std::is_integral<T>::value && sizeof(T) <= 2) rc = launch_fchain<T>(ctx, cur, vradius, span, true, !last);
-                else rc = VSZIP_ERR_ARG;
-                p += span - 1;
-            } else if (span > 1 && !vertical && hsmall_ok<T>(ctx, cur, hradius, hpasses)) {
-                if constexpr (std::is_integral<T>::value && sizeof(T) <= 2) rc = launch_hsmall<T>(ctx, cur, hradius, hpasses, !last);
-                else rc = VSZIP_ERR_ARG;
-                p += span - 1;
-            } else if (span > 1 && vertical && vsmall_ok<T>(ctx, cur, vradius, span)) {
-                if constexpr (std::is_integral<T>::value && sizeof(T) <= 2) rc = launch_vsmall<T>(ctx, cur, vradius, span, !last);
-                else rc = VSZIP_ERR_ARG;
-                p += span - 1;
-            } else {
-                if (span > 1) {  // (the planes do not qualify: back to one pass per launch; this one is not the last)
-                    span = 1;
-                    for (int i = 0; i < ng; ++i) {
-                        if (total > 1) {
-                            cur[i].dst = scratch[which] + goff[i];
-                            cur[i].dstride = (planes[g0 + i].w + 63) & ~63;
-                        }
-                    }
-                }
-                const bool last1 = p == total - 1;
-                rc = launch_pass<T>(ctx, cur, vertical ? vradius : hradius, vertical, !last1);
-            }
+            const int rc = run_step<T>(ctx, cur, st, kk_tab);
             if (rc != VSZIP_OK) return rc;
             for (int i = 0; i < ng; ++i) {
                 cur[i].src = cur[i].dst;
                 cur[i].sstride = cur[i].dstride;
             }
-            which ^= 1;
         }
-        g0 = g1;
     }
     return VSZIP_OK;
 }
