@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define VSZIP_ABI_VERSION 4 /* additive since 4: vszip_clahe, vszip_comb_mask, vszip_comb_mask_mt, vszip_checkmate, vszip_mosquito_nr, vszip_deband, vszip_deband_tables, vszip_bilateral_dither, vszip_bilateral_dither_derive, vszip_bilateral_dither_points; 4 (round 5): vszip_dev_alloc searches a bounded number of candidates and keeps nothing (below); vszip_dev_arena_info added; vszip_dev_trim, vszip_dev_placement_info and
+#define VSZIP_ABI_VERSION 4 /* additive since 4: vszip_clahe, vszip_comb_mask, vszip_comb_mask_mt, vszip_checkmate, vszip_mosquito_nr, vszip_deband, vszip_deband_tables, vszip_bilateral_dither, vszip_bilateral_dither_derive, vszip_bilateral_dither_points, vszip_compress, vszip_compress_tables; 4 (round 5): vszip_dev_alloc searches a bounded number of candidates and keeps nothing (below); vszip_dev_arena_info added; vszip_dev_trim, vszip_dev_placement_info and
                                vszip_dev_alloc_probed removed (nothing is searched for or parked any more); 3 (round 4): vszip_ctx_set_option / _get_option, vszip_dev_probe_region,
                                vszip_plane_average_async, vszip_plane_minmax_async added; 2 (round 3): vszip_ssim_source grew (YUV sources); entry points added since 1:
                                vszip_chain_run, vszip_ssimulacra2_src, vszip_to_rgbs_linear, vszip_probe_read_each, vszip_resample_table */
@@ -162,7 +162,12 @@ int vszip_probe_read_each(vszip_ctx *ctx, double *total_ms, int *launches, float
  *    the entry's plane and pitches of their own: h x offsets_pitch pairs and h x grain_pitch samples readable each; no output depends on their
  *    padding either. vszip_bilateral_dither reads a (2 radius - 1)^2 window mirrored at the plane's edges: its reads stay inside
  *    [0, w) x h of src and ref, the whole point table (23 x K pairs) is an input, only [0, w) x h of dst is written, dst must overlap no
- *    input, ref may be the very src pointer, and every base alignment and pitch takes the same path. Partial overlap is never allowed.
+ *    input, ref may be the very src pointer, and every base alignment and pitch takes the same path. vszip_compress works on 8 x 8
+ *    blocks with no neighbourhood: its reads stay inside [0, w) x h of src (a partial block at the right or bottom edge replicates the
+ *    last in-plane column or row, min(x, w - 1) / min(y, h - 1), and never reads pitch padding), only [0, w) x h of dst is written,
+ *    and dst == src (same pointer, same stride) is allowed, because a block reads and writes only its own 8 x 8 samples and is read
+ *    completely before it is stored; any other overlap is not allowed. Every base alignment and pitch is served: a fast path for
+ *    bases and pitches that are multiples of 8 bytes, and a slower one with the same bits. Partial overlap is never allowed.
  */
 typedef struct vszip_plane {
     const void *src; /* input plane */
@@ -442,6 +447,46 @@ int vszip_bilateral_dither_derive(int is_float, int bits_per_sample, int radius,
 int vszip_bilateral_dither_points(int radius, float subspl, int16_t *points, size_t capacity, int32_t *K);
 int vszip_bilateral_dither(vszip_ctx *ctx, int dtype, int bits_per_sample, const vszip_plane *planes,
                            const vszip_bilateral_dither_plane *per_plane, int nplanes);
+
+/*
+ * Compress — MPEG-2 intra or JPEG artifacts: replaces processPlane of src/filters/compress.zig:458-515 (with processBlock :432-446:
+ * fdctIslow :132-200, quantMpeg2 / dequantMpeg2 :215-254, quantJpeg / dequantJpeg :257-278, idctRows :296-356, idctColsPut :359-422)
+ * as Compress(codec).getFrame calls it per plane (src/vapoursynth/compress.zig:23-48), QuantTables.buildMpeg2 / buildJpeg
+ * (compress.zig:80-103) and the create-time checks of compressCreate (compress.zig(vs):77-110).
+ *
+ * vszip_compress_tables (device-free). The wrapper's arguments -> the tables of one clip, in natural raster order:
+ *   mpeg2 (codec 0)  qmul[p][i] = (2 << 21) / (2 qscale M[i]), deq[p][i] = 2 qscale M[i] with M the default intra matrix, both p alike;
+ *                    dc_scale = 8 >> dc_prec, dc_q = 8 dc_scale;
+ *   jpeg (codec 1)   q = clamp((base_p[i] scale + 50) / 100, 1, 255) with scale = 5000 / quality below 50, else 200 - 2 quality;
+ *                    deq[p][i] = q, qmul[p][i] = (1 << 21) / (8 q); dc_q = 64 and dc_scale = 8 are not used.
+ * VSZIP_ERR_ARG with the wrapper's wording in `err` (may be NULL), in its order, only the chosen codec's parameters being
+ * checked: "Compress: codec must be 0 (mpeg2) or 1 (jpeg).", "Compress: qscale must be between 1 and 31.", "Compress: dc_prec
+ * must be between 0 and 3.", "Compress: quality must be between 1 and 100."; also for a NULL `out`. The wrapper's defaults are
+ * codec 0, qscale 8, dc_prec 0, quality 50. (The type is `struct vszip_compress_tables`: C keeps struct tags apart from functions.)
+ *
+ * vszip_compress. 8-bit planes only; any number of planes of any sizes (w, h >= 1) in one call, so the planes of many frames fit.
+ * chroma[i] != 0 selects table index 1 for planes[i] (the wrapper passes plane != 0); NULL: all luma. `ref` is unused. Planes
+ * the wrapper does not process (chroma = False) are the host's copy. Per block: samples (jpeg: minus 128) -> forward DCT, two
+ * passes -> quantise (64-bit products; mpeg2: DC (dc + dc_q / 2) / dc_q, AC with the deadzone and the 3/8 bias; jpeg: round to
+ * nearest) -> dequantise (mpeg2: the magnitude times deq >> 4 with the sign restored, DC times dc_scale; jpeg: level times deq) ->
+ * inverse DCT, two passes, a row with nothing beyond its first coefficient taking the short cut 8 c0 -> (jpeg: plus 128) -> clamp
+ * to 0..255. Every pass stores 16-bit two's complement, all 32-bit arithmetic wraps: bit-exact with the reference. One fused pass,
+ * a block per lane, no scratch. `tables` is HOST memory and is consumed before the call returns (it travels in the kernel
+ * argument), so the caller may reuse it at once. Tables need not come from vszip_compress_tables, but must lie in the range it can
+ * produce: 0 <= qmul <= 2^20 and 0 <= deq <= 32767 (with qmul >= 0 the quantiser works on the magnitude and restores the sign).
+ * VSZIP_ERR_ARG: a NULL tables, src or dst, tables->codec outside 0..1, a multiplier outside those ranges, dc_q <= 0 with mpeg2, w
+ * or h below 1, a pitch below w.
+ * Asynchronous on the context stream. "Plane memory": reads stay inside [0, w) x h of src; only [0, w) x h of dst is written;
+ * dst == src is allowed.
+ */
+struct vszip_compress_tables {
+    int32_t codec;          /* 0 mpeg2, 1 jpeg */
+    int32_t qmul[2][64];    /* reciprocal multipliers, natural raster order; [0] luma, [1] chroma (mpeg2: both alike) */
+    int32_t deq[2][64];     /* dequantiser multipliers */
+    int32_t dc_q, dc_scale; /* mpeg2 DC: encode divisor, decode multiplier (64 / 8 >> dc_prec); unused for jpeg */
+};
+int vszip_compress_tables(int codec, int qscale, int dc_prec, int quality, struct vszip_compress_tables *out, char *err, size_t err_cap);
+int vszip_compress(vszip_ctx *ctx, const vszip_plane *planes, int nplanes, const struct vszip_compress_tables *tables, const uint8_t *chroma);
 
 /*
  * PlaneMinMax — replaces filter.minMax / minMaxRef / minMaxNoThr / minMaxNoThrRef

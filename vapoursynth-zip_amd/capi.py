@@ -75,6 +75,16 @@ class BilateralDitherPlane(C.Structure):
     _fields_ = [("radius", C.c_int32), ("m", C.c_float), ("wmax", C.c_float), ("sum_w_min", C.c_float), ("points", C.c_void_p), ("K", C.c_int32)]
 
 
+class CompressTables(C.Structure):
+    """struct vszip_compress_tables"""
+    _fields_ = [("codec", C.c_int32), ("qmul", (C.c_int32 * 64) * 2), ("deq", (C.c_int32 * 64) * 2), ("dc_q", C.c_int32), ("dc_scale", C.c_int32)]
+
+    def as_dict(self) -> dict:
+        """the fields as tests/compress_ref.py tables() names them"""
+        return dict(codec=int(self.codec), qmul=np.array(self.qmul, np.int32).reshape(2, 64), deq=np.array(self.deq, np.int32).reshape(2, 64), dc_q=int(self.dc_q),
+                    dc_scale=int(self.dc_scale))
+
+
 class BilateralCfg(C.Structure):
     _fields_ = [
         ("sigmaS", C.c_double), ("sigmaR", C.c_double), ("process", C.c_int32), ("algorithm", C.c_int32),
@@ -167,6 +177,8 @@ SYMBOLS = {
     "vszip_bilateral_dither_derive": (_i, [_i, _i, _i, C.c_float, C.c_float, C.c_float, C.c_float, C.POINTER(BilateralDitherCfg), C.c_char_p, _sz]),
     "vszip_bilateral_dither_points": (_i, [_i, C.c_float, _vp, _sz, C.POINTER(C.c_int32)]),
     "vszip_bilateral_dither": (_i, [_vp, _i, _i, _PP, C.POINTER(BilateralDitherPlane), _i]),
+    "vszip_compress_tables": (_i, [_i, _i, _i, _i, C.POINTER(CompressTables), C.c_char_p, _sz]),
+    "vszip_compress": (_i, [_vp, _PP, _i, C.POINTER(CompressTables), C.POINTER(C.c_uint8)]),
     "vszip_plane_average": (_i, [_vp, _i, _PP, _i, C.POINTER(C.c_int32), _i, _i, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "vszip_plane_minmax": (_i, [_vp, _i, _PP, _i, C.c_float, C.c_float, _i, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "vszip_plane_average_async": (_i, [_vp, _i, _PP, _i, C.POINTER(C.c_int32), _i, _i, _vp]),
@@ -238,6 +250,16 @@ def bilateral_dither_points(radius, subspl=0.0) -> np.ndarray:
     if rc != 0:
         raise ValueError(f"vszip_bilateral_dither_points({radius}, {subspl}) -> {rc}")
     return pts
+
+
+def compress_tables(codec=0, qscale=8, dc_prec=0, quality=50) -> CompressTables:
+    """vszip_compress_tables (device-free): the quantiser tables of vszip.Compress for one clip (codec 0 mpeg2 with qscale and dc_prec, 1 jpeg
+    with quality). ValueError with the reference's wording for an argument out of range."""
+    tb, err = CompressTables(), C.create_string_buffer(256)
+    rc = load().vszip_compress_tables(int(codec), int(qscale), int(dc_prec), int(quality), C.byref(tb), err, len(err))
+    if rc != 0:
+        raise ValueError(err.value.decode() or f"vszip_compress_tables -> {rc}")
+    return tb
 
 
 def _share_torch_hip_runtime():
@@ -654,6 +676,27 @@ class Device:
     def prepared_mosquito_nr(self, srcs, dsts, strength=16, restore=128, radius=2, bits=None, chroma=None):
         """-> a callable queueing vszip_mosquito_nr on argument blocks built once."""
         fn, ctx, check, args = self.lib.vszip_mosquito_nr, self.ctx, self.check, self._mosquito_args(srcs, dsts, strength, restore, radius, bits, chroma)
+        return lambda: check(fn(ctx, *args))
+
+    def _compress_args(self, srcs, dsts, tables, chroma):
+        n = len(srcs)
+        if len(dsts) != n or any(s.dtype != np.uint8 for s in srcs):
+            raise ValueError("compress: one destination per plane, 8-bit planes only")
+        ch = None
+        if chroma is not None:
+            ch = (C.c_uint8 * n)(*([int(bool(chroma))] * n if isinstance(chroma, (bool, int, np.integer)) else [int(bool(c)) for c in chroma]))
+            if len(ch) != n:
+                raise ValueError("compress: chroma is a scalar or one value per plane")
+        return (self.plane_table(srcs, dsts), n, C.byref(tables) if tables is not None else None, ch)
+
+    def compress(self, srcs, dsts, tables, chroma=None):
+        """vszip.Compress on every plane of srcs (u8, any sizes): tables from compress_tables(); chroma a scalar or one value per plane
+        (true: the chroma tables), None = all luma. dsts[i] may be srcs[i] itself."""
+        self.check(self.lib.vszip_compress(self.ctx, *self._compress_args(srcs, dsts, tables, chroma)))
+
+    def prepared_compress(self, srcs, dsts, tables, chroma=None):
+        """-> a callable queueing vszip_compress on argument blocks built once."""
+        fn, ctx, check, args = self.lib.vszip_compress, self.ctx, self.check, self._compress_args(srcs, dsts, tables, chroma)
         return lambda: check(fn(ctx, *args))
 
     def upload_deband_tables(self, tab: dict) -> dict:

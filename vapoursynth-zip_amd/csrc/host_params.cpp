@@ -567,3 +567,49 @@ VSZIP_EXPORT int vszip_bilateral_dither_points(int radius, float subspl, int16_t
     }
     return VSZIP_OK;
 }
+
+// ---- Compress: the quantiser tables of one clip (QuantTables.buildMpeg2 / buildJpeg, src/filters/compress.zig:80-103) and the
+// create-time checks of compressCreate (src/vapoursynth/compress.zig:77-110), in its order ----
+namespace {
+// natural raster order: the MPEG-1/2 default intra matrix (luma and chroma), the JPEG Annex K luminance and chrominance tables
+const int kMpegIntra[64] = {8,  16, 19, 22, 26, 27, 29, 34, 16, 16, 22, 24, 27, 29, 34, 37, 19, 22, 26, 27, 29, 34, 34, 38, 22, 22, 26, 27, 29, 34, 37, 40,
+                            22, 26, 27, 29, 32, 35, 40, 48, 26, 27, 29, 32, 35, 40, 48, 58, 26, 27, 29, 34, 38, 46, 56, 69, 27, 29, 35, 38, 46, 56, 69, 83};
+const int kJpegBase[2][64] = {{16, 11, 10, 16, 24, 40, 51, 61,  12, 12, 14, 19, 26, 58,  60,  55,  14, 13, 16, 24, 40,  57,  69,  56,  14, 17, 22, 29, 51,  87,  80,  62,
+                               18, 22, 37, 56, 68, 109, 103, 77, 24, 35, 55, 64, 81, 104, 113, 92,  49, 64, 78, 87, 103, 121, 120, 101, 72, 92, 95, 98, 112, 100, 103, 99},
+                              {17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99, 24, 26, 56, 99, 99, 99, 99, 99, 47, 66, 99, 99, 99, 99, 99, 99,
+                               99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99}};
+
+int compress_error(char *err, size_t cap, const char *text) {
+    if (err && cap) std::snprintf(err, cap, "Compress: %s", text);
+    return VSZIP_ERR_ARG;
+}
+}  // namespace
+
+VSZIP_EXPORT int vszip_compress_tables(int codec, int qscale, int dc_prec, int quality, struct vszip_compress_tables *out, char *err, size_t err_cap) {
+    if (!out) return compress_error(err, err_cap, "out must not be NULL");
+    if (codec < 0 || codec > 1) return compress_error(err, err_cap, "codec must be 0 (mpeg2) or 1 (jpeg).");
+    out->codec = codec;
+    out->dc_q = 64;
+    out->dc_scale = 8;
+    if (codec == 0) {
+        if (qscale < 1 || qscale > 31) return compress_error(err, err_cap, "qscale must be between 1 and 31.");
+        if (dc_prec < 0 || dc_prec > 3) return compress_error(err, err_cap, "dc_prec must be between 0 and 3.");
+        for (int i = 0; i < 64; ++i) {
+            const int den = (qscale << 1) * kMpegIntra[i];
+            out->qmul[0][i] = out->qmul[1][i] = (int32_t)(((int64_t)2 << 21) / den);
+            out->deq[0][i] = out->deq[1][i] = den;
+        }
+        out->dc_scale = 8 >> dc_prec;
+        out->dc_q = out->dc_scale << 3;
+    } else {
+        if (quality < 1 || quality > 100) return compress_error(err, err_cap, "quality must be between 1 and 100.");
+        const int scale = quality < 50 ? 5000 / quality : 200 - quality * 2;
+        for (int p = 0; p < 2; ++p)
+            for (int i = 0; i < 64; ++i) {
+                const int q = std::min(std::max((kJpegBase[p][i] * scale + 50) / 100, 1), 255);
+                out->deq[p][i] = q;
+                out->qmul[p][i] = (int32_t)(((int64_t)1 << 21) / (8 * q));
+            }
+    }
+    return VSZIP_OK;
+}
