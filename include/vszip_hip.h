@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define VSZIP_ABI_VERSION 4 /* additive since 4: vszip_clahe, vszip_comb_mask, vszip_comb_mask_mt, vszip_checkmate, vszip_mosquito_nr, vszip_deband, vszip_deband_tables, vszip_bilateral_dither, vszip_bilateral_dither_derive, vszip_bilateral_dither_points, vszip_compress, vszip_compress_tables; 4 (round 5): vszip_dev_alloc searches a bounded number of candidates and keeps nothing (below); vszip_dev_arena_info added; vszip_dev_trim, vszip_dev_placement_info and
+#define VSZIP_ABI_VERSION 4 /* additive since 4: vszip_clahe, vszip_comb_mask, vszip_comb_mask_mt, vszip_checkmate, vszip_mosquito_nr, vszip_deband, vszip_deband_tables, vszip_bilateral_dither, vszip_bilateral_dither_derive, vszip_bilateral_dither_points, vszip_compress, vszip_compress_tables, vszip_pack_rgb, vszip_color_map_lut, vszip_color_map; 4 (round 5): vszip_dev_alloc searches a bounded number of candidates and keeps nothing (below); vszip_dev_arena_info added; vszip_dev_trim, vszip_dev_placement_info and
                                vszip_dev_alloc_probed removed (nothing is searched for or parked any more); 3 (round 4): vszip_ctx_set_option / _get_option, vszip_dev_probe_region,
                                vszip_plane_average_async, vszip_plane_minmax_async added; 2 (round 3): vszip_ssim_source grew (YUV sources); entry points added since 1:
                                vszip_chain_run, vszip_ssimulacra2_src, vszip_to_rgbs_linear, vszip_probe_read_each, vszip_resample_table */
@@ -168,6 +168,12 @@ int vszip_probe_read_each(vszip_ctx *ctx, double *total_ms, int *launches, float
  *    and dst == src (same pointer, same stride) is allowed, because a block reads and writes only its own 8 x 8 samples and is read
  *    completely before it is stored; any other overlap is not allowed. Every base alignment and pitch is served: a fast path for
  *    bases and pitches that are multiples of 8 bytes, and a slower one with the same bits. Partial overlap is never allowed.
+ *    vszip_pack_rgb and vszip_color_map are point filters whose planes differ in number and sample width (three planes in and one
+ *    32-bit plane out; one plane in and three out): their reads stay inside [0, w) x h of every input (pitch padding is never read),
+ *    only [0, w) x h of every output is written, r, g and b of vszip_pack_rgb may be the very same pointer or overlap each other,
+ *    no output may overlap an input, and the three outputs of vszip_color_map must not overlap each other. Every base alignment of
+ *    the sample type and every pitch >= w is served: a fast path for bases and pitches (in bytes) that are multiples of 16 on every
+ *    plane of the frame, and a slower one with the same bits.
  */
 typedef struct vszip_plane {
     const void *src; /* input plane */
@@ -487,6 +493,59 @@ struct vszip_compress_tables {
 };
 int vszip_compress_tables(int codec, int qscale, int dc_prec, int quality, struct vszip_compress_tables *out, char *err, size_t err_cap);
 int vszip_compress(vszip_ctx *ctx, const vszip_plane *planes, int nplanes, const struct vszip_compress_tables *tables, const uint8_t *chroma);
+
+/*
+ * PackRGB — planar RGB to one packed 32-bit plane for a previewer: replaces the two loops of Pack(is_rgb24).getFrame
+ * (src/vapoursynth/packrgb.zig:33-63) and the format check of packrgbCreate (:88-97). One vszip_pack_rgb_frame per frame: r, g, b are
+ * uint8_t planes (bits 8, RGB24) or uint16_t planes (bits 10, RGB30) of w x h samples with a pitch each, dst is the packed plane of
+ * w x h uint32_t; all strides in elements of the plane's own sample type (dst_stride in 32-bit elements). Any number of frames of any
+ * mix of sizes in one call. bits 8: dst = b | g << 8 | r << 16 | 255 << 24, in memory the bytes B, G, R, 0xFF. bits 10:
+ * dst = b | g << 10 | r << 20 | 3 << 30 in uint32_t arithmetic, exactly as :60 writes it: nothing is masked, so a 16-bit sample above
+ * 1023 runs into the neighbouring field and what is shifted beyond bit 31 is lost, as in the reference; that is not an error.
+ * One streaming pass, no scratch. Asynchronous on the context stream. VSZIP_ERR_ARG: bits other than 8 or 10 ("PackRGB: only RGB24 and
+ * RGB30 inputs are supported!", the reference's text), and, naming the frame ("PackRGB: frame 1: r, g, b and dst must not be NULL"), a
+ * NULL plane, w or h below 1, a pitch below w. "Plane memory": reads stay inside [0, w) x h of r, g and b; only [0, w) x h of dst is
+ * written; r, g and b may alias each other; dst may overlap no input.
+ */
+typedef struct vszip_pack_rgb_frame {
+    const void *r, *g, *b; /* uint8_t (bits 8) or uint16_t (bits 10) planes, w x h each */
+    ptrdiff_t r_stride, g_stride, b_stride;
+    uint32_t *dst; /* w x h packed samples */
+    ptrdiff_t dst_stride;
+    int32_t w, h;
+} vszip_pack_rgb_frame;
+int vszip_pack_rgb(vszip_ctx *ctx, int bits, const vszip_pack_rgb_frame *frames, int nframes);
+
+/*
+ * ColorMap — Gray8 to false-colour RGB24 through a 256-entry table per channel: replaces the loop of colorMapGetFrame
+ * (src/vapoursynth/color_map.zig:36-46) and the table build of colorMapCreate (:92-103). The palettes (the reference's 22 tables of
+ * src/filters/color_map.zig) and the `color` range check 0..21 stay with the host that binds this library; the
+ * frame properties of :48-52 are the host's, too.
+ *
+ * vszip_color_map_lut (host only, device-free). A palette of `len` points a channel (f32, nominally 0..1) -> lut[c][i], i = 0..255:
+ * p = ((float)i * (float)(len - 1)) / 255.0f (a multiply, then a divide, both rounded to f32), lo = floor(p), hi = min(lo + 1, len - 1),
+ * frac = p - lo, v = c[lo] + (c[hi] - c[lo]) * frac (the multiply and the add each rounded, never fused),
+ * lut = trunc(fmaf(v, 255.0f, 0.5f)) (one fused operation). VSZIP_ERR_ARG, with the channel and the index in `err` (may be NULL):
+ * len below 1 (or above 2^24), a NULL argument, and a table entry that is NaN or lands outside 0..255 (the reference's @trunc to u8
+ * is undefined there), e.g. "ColorMap: g: table entry 255 (palette points 3 and 3) gives 258.05, outside 0..255".
+ *
+ * vszip_color_map. One vszip_color_map_frame per frame: src is a uint8_t plane of w x h, r, g, b the three output planes, a pitch
+ * each; any number of frames of any mix of sizes in one call. Per sample s: r = lut[0][s], g = lut[1][s], b = lut[2][s]. `lut` is HOST
+ * memory and is consumed before the call returns (it travels in the kernel argument), so the caller may overwrite it at once; it need
+ * not come from vszip_color_map_lut. One streaming pass with the table in LDS, no scratch. Asynchronous on the context stream.
+ * VSZIP_ERR_ARG: a NULL lut, and, naming the frame ("ColorMap: frame 1: src, r, g and b must not be NULL"), a NULL plane, w or h
+ * below 1, a pitch below w. "Plane memory": reads stay inside [0, w) x h of src; only [0, w) x h of r, g and b is written; the three
+ * outputs overlap neither each other nor src.
+ */
+typedef struct vszip_color_map_frame {
+    const uint8_t *src;
+    ptrdiff_t src_stride;
+    uint8_t *r, *g, *b;
+    ptrdiff_t r_stride, g_stride, b_stride;
+    int32_t w, h;
+} vszip_color_map_frame;
+int vszip_color_map_lut(const float *r, const float *g, const float *b, int len, uint8_t lut[3][256], char *err, size_t err_cap);
+int vszip_color_map(vszip_ctx *ctx, const vszip_color_map_frame *frames, int nframes, const uint8_t lut[3][256]);
 
 /*
  * PlaneMinMax — replaces filter.minMax / minMaxRef / minMaxNoThr / minMaxNoThrRef

@@ -85,6 +85,18 @@ class CompressTables(C.Structure):
                     dc_scale=int(self.dc_scale))
 
 
+class PackRGBFrame(C.Structure):
+    """vszip_pack_rgb_frame"""
+    _fields_ = [("r", C.c_void_p), ("g", C.c_void_p), ("b", C.c_void_p), ("r_stride", C.c_ssize_t), ("g_stride", C.c_ssize_t), ("b_stride", C.c_ssize_t),
+                ("dst", C.c_void_p), ("dst_stride", C.c_ssize_t), ("w", C.c_int32), ("h", C.c_int32)]
+
+
+class ColorMapFrame(C.Structure):
+    """vszip_color_map_frame"""
+    _fields_ = [("src", C.c_void_p), ("src_stride", C.c_ssize_t), ("r", C.c_void_p), ("g", C.c_void_p), ("b", C.c_void_p),
+                ("r_stride", C.c_ssize_t), ("g_stride", C.c_ssize_t), ("b_stride", C.c_ssize_t), ("w", C.c_int32), ("h", C.c_int32)]
+
+
 class BilateralCfg(C.Structure):
     _fields_ = [
         ("sigmaS", C.c_double), ("sigmaR", C.c_double), ("process", C.c_int32), ("algorithm", C.c_int32),
@@ -179,6 +191,9 @@ SYMBOLS = {
     "vszip_bilateral_dither": (_i, [_vp, _i, _i, _PP, C.POINTER(BilateralDitherPlane), _i]),
     "vszip_compress_tables": (_i, [_i, _i, _i, _i, C.POINTER(CompressTables), C.c_char_p, _sz]),
     "vszip_compress": (_i, [_vp, _PP, _i, C.POINTER(CompressTables), C.POINTER(C.c_uint8)]),
+    "vszip_pack_rgb": (_i, [_vp, _i, C.POINTER(PackRGBFrame), _i]),
+    "vszip_color_map_lut": (_i, [C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), _i, _vp, C.c_char_p, _sz]),
+    "vszip_color_map": (_i, [_vp, C.POINTER(ColorMapFrame), _i, _vp]),
     "vszip_plane_average": (_i, [_vp, _i, _PP, _i, C.POINTER(C.c_int32), _i, _i, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "vszip_plane_minmax": (_i, [_vp, _i, _PP, _i, C.c_float, C.c_float, _i, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "vszip_plane_average_async": (_i, [_vp, _i, _PP, _i, C.POINTER(C.c_int32), _i, _i, _vp]),
@@ -260,6 +275,21 @@ def compress_tables(codec=0, qscale=8, dc_prec=0, quality=50) -> CompressTables:
     if rc != 0:
         raise ValueError(err.value.decode() or f"vszip_compress_tables -> {rc}")
     return tb
+
+
+def color_map_lut(r, g, b) -> np.ndarray:
+    """vszip_color_map_lut (device-free): a palette of len(r) points a channel (f32, 0..1) -> the (3, 256) uint8 table of vszip.ColorMap,
+    interpolated and rounded as the reference's create function does. VszipError (VSZIP_ERR_ARG) naming the channel and the index for an empty
+    palette and for an entry that is NaN or lands outside 0..255."""
+    pal = [np.ascontiguousarray(c, np.float32).reshape(-1) for c in (r, g, b)]
+    if not (len(pal[0]) == len(pal[1]) == len(pal[2])):
+        raise ValueError("color_map_lut: r, g and b have one length")
+    fp = lambda a: a.ctypes.data_as(C.POINTER(C.c_float))
+    lut, err = np.zeros((3, 256), np.uint8), C.create_string_buffer(256)
+    rc = load().vszip_color_map_lut(fp(pal[0]), fp(pal[1]), fp(pal[2]), len(pal[0]), lut.ctypes.data, err, len(err))
+    if rc != 0:
+        raise VszipError(rc, err.value.decode() or f"vszip_color_map_lut -> {rc}")
+    return lut
 
 
 def _share_torch_hip_runtime():
@@ -698,6 +728,52 @@ class Device:
         """-> a callable queueing vszip_compress on argument blocks built once."""
         fn, ctx, check, args = self.lib.vszip_compress, self.ctx, self.check, self._compress_args(srcs, dsts, tables, chroma)
         return lambda: check(fn(ctx, *args))
+
+    def _pack_rgb_args(self, rs, gs, bs, dsts, bits):
+        n = len(rs)
+        if not (len(gs) == len(bs) == len(dsts) == n):
+            raise ValueError("pack_rgb: one g, b and dst plane per r plane")
+        want = {8: np.uint8, 10: np.uint16}.get(int(bits))
+        if want is not None and any(p.dtype != want for p in (*rs, *gs, *bs)):
+            raise ValueError(f"pack_rgb: bits={bits} takes {np.dtype(want).name} planes")
+        if any(d.dtype != np.uint32 for d in dsts):
+            raise ValueError("pack_rgb: dst planes are uint32")
+        arr = (PackRGBFrame * n)()
+        for i in range(n):
+            arr[i] = PackRGBFrame(rs[i].ptr, gs[i].ptr, bs[i].ptr, rs[i].stride, gs[i].stride, bs[i].stride, dsts[i].ptr, dsts[i].stride, dsts[i].w, dsts[i].h)
+        return (int(bits), arr, n)
+
+    def pack_rgb(self, rs, gs, bs, dsts, bits=8):
+        """vszip.PackRGB on every frame: rs / gs / bs the planes of RGB24 (u8, bits=8) or RGB30 (u16, bits=10), dsts the packed u32 planes
+        (b | g << 8 | r << 16 | 255 << 24, or b | g << 10 | r << 20 | 3 << 30); any mix of sizes. The inputs may alias each other."""
+        self.check(self.lib.vszip_pack_rgb(self.ctx, *self._pack_rgb_args(rs, gs, bs, dsts, bits)))
+
+    def prepared_pack_rgb(self, rs, gs, bs, dsts, bits=8):
+        """-> a callable queueing vszip_pack_rgb on argument blocks built once."""
+        fn, ctx, check, args = self.lib.vszip_pack_rgb, self.ctx, self.check, self._pack_rgb_args(rs, gs, bs, dsts, bits)
+        return lambda: check(fn(ctx, *args))
+
+    def _color_map_args(self, srcs, rs, gs, bs, lut):
+        n = len(srcs)
+        if not (len(rs) == len(gs) == len(bs) == n) or any(p.dtype != np.uint8 for p in (*srcs, *rs, *gs, *bs)):
+            raise ValueError("color_map: one r, g and b plane per source plane, 8-bit planes only")
+        if lut is not None and (not isinstance(lut, np.ndarray) or lut.dtype != np.uint8 or lut.shape != (3, 256) or not lut.flags.c_contiguous):
+            raise ValueError("color_map: lut is a C-contiguous (3, 256) uint8 array (color_map_lut)")
+        arr = (ColorMapFrame * n)()
+        for i in range(n):
+            arr[i] = ColorMapFrame(srcs[i].ptr, srcs[i].stride, rs[i].ptr, gs[i].ptr, bs[i].ptr, rs[i].stride, gs[i].stride, bs[i].stride, srcs[i].w, srcs[i].h)
+        return (arr, n, lut)
+
+    def color_map(self, srcs, rs, gs, bs, lut):
+        """vszip.ColorMap on every frame: srcs Gray8 planes, rs / gs / bs the planes of the RGB24 result, lut the (3, 256) uint8 table of
+        color_map_lut() (consumed before the call returns); any mix of sizes."""
+        arr, n, lut = self._color_map_args(srcs, rs, gs, bs, lut)
+        self.check(self.lib.vszip_color_map(self.ctx, arr, n, lut.ctypes.data if lut is not None else None))
+
+    def prepared_color_map(self, srcs, rs, gs, bs, lut):
+        """-> a callable queueing vszip_color_map on argument blocks built once (the table is read at every call)."""
+        fn, ctx, check, (arr, n, lut) = self.lib.vszip_color_map, self.ctx, self.check, self._color_map_args(srcs, rs, gs, bs, lut)
+        return lambda: check(fn(ctx, arr, n, lut.ctypes.data))
 
     def upload_deband_tables(self, tab: dict) -> dict:
         """The tables of deband_tables() (or of the numpy spec) resident on the device, uploaded once per clip: `luma` / `chroma` as

@@ -613,3 +613,36 @@ VSZIP_EXPORT int vszip_compress_tables(int codec, int qscale, int dc_prec, int q
     }
     return VSZIP_OK;
 }
+
+// ---- ColorMap: the 256-entry table of one palette (colorMapCreate, src/vapoursynth/color_map.zig:92-103), with its roundings ----
+VSZIP_EXPORT int vszip_color_map_lut(const float *r, const float *g, const float *b, int len, uint8_t lut[3][256], char *err, size_t err_cap) {
+    if (err && err_cap) err[0] = 0;
+    if (!r || !g || !b || !lut) {
+        if (err && err_cap) std::snprintf(err, err_cap, "ColorMap: r, g, b and lut must not be NULL");
+        return VSZIP_ERR_ARG;
+    }
+    if (len < 1 || len > (1 << 24)) {
+        if (err && err_cap) std::snprintf(err, err_cap, "ColorMap: len = %d, a palette has 1 .. 16777216 points", len);
+        return VSZIP_ERR_ARG;
+    }
+    const float *pal[3] = {r, g, b};
+    const float lenm1 = (float)(len - 1);
+    for (int i = 0; i < 256; ++i) {
+        const volatile float scaled = (float)i * lenm1;  // volatile: every operation of the interpolation is rounded to f32 on its own, whatever
+        const float p = scaled / 255.0f;                 // the compiler's contraction rule is (the reference's multiply and add are not fused)
+        const int lo = (int)std::floor(p), hi = std::min(lo + 1, len - 1);
+        const float frac = p - (float)lo;
+        for (int c = 0; c < 3; ++c) {
+            const volatile float d = pal[c][hi] - pal[c][lo];
+            const volatile float prod = d * frac;
+            const volatile float v = pal[c][lo] + prod;
+            const float t = std::fmaf(v, 255.0f, 0.5f);  // the reference's @mulAdd: one rounding
+            if (!(t > -1.0f && t < 256.0f)) {
+                if (err && err_cap) std::snprintf(err, err_cap, "ColorMap: %c: table entry %d (palette points %d and %d) gives %g, outside 0..255", "rgb"[c], i, lo, hi, (double)t);
+                return VSZIP_ERR_ARG;
+            }
+            lut[c][i] = (uint8_t)(int)t;  // truncation towards zero
+        }
+    }
+    return VSZIP_OK;
+}
