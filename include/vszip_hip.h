@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define VSZIP_ABI_VERSION 4 /* additive since 4: vszip_clahe, vszip_comb_mask, vszip_comb_mask_mt, vszip_checkmate, vszip_mosquito_nr, vszip_deband, vszip_deband_tables, vszip_bilateral_dither, vszip_bilateral_dither_derive, vszip_bilateral_dither_points, vszip_compress, vszip_compress_tables, vszip_pack_rgb, vszip_color_map_lut, vszip_color_map; 4 (round 5): vszip_dev_alloc searches a bounded number of candidates and keeps nothing (below); vszip_dev_arena_info added; vszip_dev_trim, vszip_dev_placement_info and
+#define VSZIP_ABI_VERSION 4 /* additive since 4: vszip_clahe, vszip_comb_mask, vszip_comb_mask_mt, vszip_checkmate, vszip_mosquito_nr, vszip_deband, vszip_deband_tables, vszip_bilateral_dither, vszip_bilateral_dither_derive, vszip_bilateral_dither_points, vszip_compress, vszip_compress_tables, vszip_pack_rgb, vszip_color_map_lut, vszip_color_map, vszip_image_unpack; 4 (round 5): vszip_dev_alloc searches a bounded number of candidates and keeps nothing (below); vszip_dev_arena_info added; vszip_dev_trim, vszip_dev_placement_info and
                                vszip_dev_alloc_probed removed (nothing is searched for or parked any more); 3 (round 4): vszip_ctx_set_option / _get_option, vszip_dev_probe_region,
                                vszip_plane_average_async, vszip_plane_minmax_async added; 2 (round 3): vszip_ssim_source grew (YUV sources); entry points added since 1:
                                vszip_chain_run, vszip_ssimulacra2_src, vszip_to_rgbs_linear, vszip_probe_read_each, vszip_resample_table */
@@ -173,7 +173,11 @@ int vszip_probe_read_each(vszip_ctx *ctx, double *total_ms, int *launches, float
  *    only [0, w) x h of every output is written, r, g and b of vszip_pack_rgb may be the very same pointer or overlap each other,
  *    no output may overlap an input, and the three outputs of vszip_color_map must not overlap each other. Every base alignment of
  *    the sample type and every pitch >= w is served: a fast path for bases and pitches (in bytes) that are multiples of 16 on every
- *    plane of the frame, and a slower one with the same bits.
+ *    plane of the frame, and a slower one with the same bits. vszip_image_unpack is the mirror of vszip_pack_rgb, one packed buffer in
+ *    and up to four planes out: its reads stay inside the w x pixel-bytes of each of the h source rows (the source's pitch is in bytes
+ *    and its padding is never read), only [0, w) x h of each output plane is written, and the outputs overlap neither each other nor
+ *    src. The source needs no alignment at all; frames whose output bases and pitches (in bytes) are multiples of 16 take the fast
+ *    path, every other frame a slower one with the same bits.
  */
 typedef struct vszip_plane {
     const void *src; /* input plane */
@@ -546,6 +550,51 @@ typedef struct vszip_color_map_frame {
 } vszip_color_map_frame;
 int vszip_color_map_lut(const float *r, const float *g, const float *b, int len, uint8_t lut[3][256], char *err, size_t err_cap);
 int vszip_color_map(vszip_ctx *ctx, const vszip_color_map_frame *frames, int nframes, const uint8_t lut[3][256]);
+
+/*
+ * ImageUnpack — a decoder's packed, interleaved pixels to planes plus an alpha plane: replaces copyPixels and copyPixelsIndexed
+ * (src/vapoursynth/image_read.zig:38-91) behind the switch of Read(alpha).getFrame (:285-345); the mirror of PackRGB. Reading, URL fetch,
+ * decoding, the PNG colour chunks and every frame property stay with the host. One vszip_image_unpack_frame per
+ * frame: src holds h rows of w pixels, a pixel's channels interleaved in the order the layout's name spells in memory; p[] and a are
+ * the output planes of `dtype` samples. Planes are filled by NAME, as copyPixels reads .r / .g / .b: p[0] receives R (for BGR / BGRA
+ * the pixel's third sample), p[1] G, p[2] B, a the alpha; the grey layouts write p[0] only and ignore p[1], p[2]. a == NULL drops the
+ * channel; a is ignored by the layouts without alpha (GRAY, RGB, BGR). Any number of frames of any mix of sizes in one call, one
+ * layout and type per call.
+ *
+ * src_stride is the one stride of this ABI given in BYTES (a 3-byte pixel does not divide a row pitch, and BMP rows are padded to 4
+ * bytes); it is at least w x pixel bytes, which is what a dense zigimg image has. p_stride[] and a_stride are in samples of `dtype`.
+ * src needs no alignment at all.
+ *
+ * Served (layout, dtype, src_bits), the arms of the reference's switch and no others; everything else is VSZIP_ERR_ARG:
+ *   GRAY        VSZIP_U8  1 | 2 | 4 | 8   grayscale1 / 2 / 4 / 8          GRAY_ALPHA  VSZIP_U8 8 | VSZIP_U16 16   grayscale8Alpha / 16Alpha
+ *   GRAY        VSZIP_U16 16              grayscale16                     RGB, RGBA   VSZIP_U8 8 | VSZIP_U16 16   rgb24 / rgba32 / rgb48 / rgba64
+ *   BGR, BGRA   VSZIP_U8  8               bgr24 / bgra32                  RGBA        VSZIP_F32 32                float32 (four f32 a pixel)
+ *   INDEXED     VSZIP_U8  8               indexed1 / 2 / 4 / 8: one index BYTE a pixel (zigimg's storage), palette = 256 x (R, G, B, A)
+ * (BGR / BGRA with 16-bit samples, RGB / BGR / BGRA / the grey layouts with float samples: refused, the reference has no such format.)
+ * Grey below 8 bits (scaleSample, :33-36): one sample a byte, the value in the low src_bits bits, higher bits ignored, output
+ * v x 255 / (2^bits - 1), that is x 255, x 85, x 17. Everywhere else src_bits equals the sample width and samples pass through bit
+ * for bit; float samples pass as bits, NaN payloads kept. `palette` is HOST memory, always 256 entries (no index can leave it; the host
+ * fills the entries its image does not define) and is consumed before the call returns (it travels in the kernel argument); it is NULL
+ * for every other layout. indexed16 is not served (the reference writes the palette's 8-bit channels into 16-bit planes; DESIGN.md
+ * 3.17): an index width other than 8 is VSZIP_ERR_ARG with a text that says so.
+ *
+ * One streaming pass, no scratch. Asynchronous on the context stream. VSZIP_ERR_ARG: a combination that is not served, a palette
+ * where none belongs or none where one does, and, naming the frame ("ImageUnpack: frame 1: src, p[0], p[1] and p[2] must not be
+ * NULL"), a NULL required plane, w or h below 1, a plane pitch below w, a source pitch below the row's bytes. "Plane memory": reads stay
+ * inside the w x pixel-bytes of each of the h source rows (source pitch padding is never read); only [0, w) x h of each output plane
+ * is written; the outputs overlap neither each other nor src. Every base and pitch is served: a fast path for frames whose output
+ * bases and pitches (in bytes) are multiples of 16, and a slower one with the same bits.
+ */
+enum { VSZIP_IMG_GRAY = 0, VSZIP_IMG_GRAY_ALPHA = 1, VSZIP_IMG_RGB = 2, VSZIP_IMG_RGBA = 3, VSZIP_IMG_BGR = 4, VSZIP_IMG_BGRA = 5, VSZIP_IMG_INDEXED = 6 };
+typedef struct vszip_image_unpack_frame {
+    const void *src;      /* w x h packed pixels, channels interleaved in the layout's memory order */
+    ptrdiff_t src_stride; /* in BYTES */
+    void *p[3];           /* p[0]: grey or R; p[1], p[2]: G, B (ignored for the grey layouts) */
+    void *a;              /* alpha plane, or NULL: the channel is dropped */
+    ptrdiff_t p_stride[3], a_stride; /* in samples of the output type */
+    int32_t w, h;
+} vszip_image_unpack_frame;
+int vszip_image_unpack(vszip_ctx *ctx, int layout, int dtype, int src_bits, const vszip_image_unpack_frame *frames, int nframes, const uint8_t palette[256][4]);
 
 /*
  * PlaneMinMax — replaces filter.minMax / minMaxRef / minMaxNoThr / minMaxNoThrRef

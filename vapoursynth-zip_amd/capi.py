@@ -97,6 +97,15 @@ class ColorMapFrame(C.Structure):
                 ("r_stride", C.c_ssize_t), ("g_stride", C.c_ssize_t), ("b_stride", C.c_ssize_t), ("w", C.c_int32), ("h", C.c_int32)]
 
 
+class ImageUnpackFrame(C.Structure):
+    """vszip_image_unpack_frame"""
+    _fields_ = [("src", C.c_void_p), ("src_stride", C.c_ssize_t), ("p", C.c_void_p * 3), ("a", C.c_void_p), ("p_stride", C.c_ssize_t * 3), ("a_stride", C.c_ssize_t),
+                ("w", C.c_int32), ("h", C.c_int32)]
+
+
+IMG_GRAY, IMG_GRAY_ALPHA, IMG_RGB, IMG_RGBA, IMG_BGR, IMG_BGRA, IMG_INDEXED = range(7)
+
+
 class BilateralCfg(C.Structure):
     _fields_ = [
         ("sigmaS", C.c_double), ("sigmaR", C.c_double), ("process", C.c_int32), ("algorithm", C.c_int32),
@@ -194,6 +203,7 @@ SYMBOLS = {
     "vszip_pack_rgb": (_i, [_vp, _i, C.POINTER(PackRGBFrame), _i]),
     "vszip_color_map_lut": (_i, [C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), _i, _vp, C.c_char_p, _sz]),
     "vszip_color_map": (_i, [_vp, C.POINTER(ColorMapFrame), _i, _vp]),
+    "vszip_image_unpack": (_i, [_vp, _i, _i, _i, C.POINTER(ImageUnpackFrame), _i, _vp]),
     "vszip_plane_average": (_i, [_vp, _i, _PP, _i, C.POINTER(C.c_int32), _i, _i, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "vszip_plane_minmax": (_i, [_vp, _i, _PP, _i, C.c_float, C.c_float, _i, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "vszip_plane_average_async": (_i, [_vp, _i, _PP, _i, C.POINTER(C.c_int32), _i, _i, _vp]),
@@ -774,6 +784,36 @@ class Device:
         """-> a callable queueing vszip_color_map on argument blocks built once (the table is read at every call)."""
         fn, ctx, check, (arr, n, lut) = self.lib.vszip_color_map, self.ctx, self.check, self._color_map_args(srcs, rs, gs, bs, lut)
         return lambda: check(fn(ctx, arr, n, lut.ctypes.data))
+
+    def _image_unpack_args(self, srcs, planes, alphas, layout, src_bits, palette):
+        n = len(srcs)
+        if not (len(planes) == len(alphas) == n) or any(s.dtype != np.uint8 for s in srcs):
+            raise ValueError("image_unpack: one list of planes and one alpha plane (or None) per source, sources as uint8 planes of row bytes")
+        dt = planes[0][0].dtype if n else np.dtype(np.uint8)
+        if any(p.dtype != dt for ps, a in zip(planes, alphas) for p in [*ps, *([a] if a is not None else [])]):
+            raise ValueError("image_unpack: the planes of a call have one sample type")
+        if palette is not None and not (isinstance(palette, np.ndarray) and palette.dtype == np.uint8 and palette.shape == (256, 4) and palette.flags.c_contiguous):
+            raise ValueError("image_unpack: palette is a C-contiguous (256, 4) uint8 array")
+        arr = (ImageUnpackFrame * n)()
+        for i, (s, ps, a) in enumerate(zip(srcs, planes, alphas)):
+            ps = list(ps) + [None] * (3 - len(ps))
+            arr[i] = ImageUnpackFrame(s.ptr, s.stride, (C.c_void_p * 3)(*[p.ptr if p is not None else None for p in ps]), a.ptr if a is not None else None,
+                                      (C.c_ssize_t * 3)(*[p.stride if p is not None else 0 for p in ps]), a.stride if a is not None else 0, ps[0].w, ps[0].h)
+        return int(layout), _NP2DT[dt] if dt != np.dtype(np.uint32) else F32, int(dt.itemsize * 8 if src_bits is None else src_bits), arr, n, palette
+
+    def image_unpack(self, srcs, planes, alphas, layout, src_bits=None, palette=None):
+        """vszip.ImageRead's pixel loop on every frame: srcs the packed pixels as uint8 planes (h rows of w x pixel bytes; their stride is the
+        source pitch in BYTES), planes[i] the one (grey) or three (R, G, B) output planes of frame i, alphas[i] its alpha plane or None, layout
+        one of IMG_*; src_bits defaults to the sample width (1 / 2 / 4 for grey below 8 bits); palette the (256, 4) uint8 R, G, B, A table of
+        IMG_INDEXED (consumed before the call returns). Float samples travel as uint32 or float32 planes. A frame's size is its first plane's."""
+        layout, dt, bits, arr, n, palette = self._image_unpack_args(srcs, planes, alphas, layout, src_bits, palette)
+        self.check(self.lib.vszip_image_unpack(self.ctx, layout, dt, bits, arr, n, palette.ctypes.data if palette is not None else None))
+
+    def prepared_image_unpack(self, srcs, planes, alphas, layout, src_bits=None, palette=None):
+        """-> a callable queueing vszip_image_unpack on argument blocks built once (the palette is read at every call)."""
+        fn, ctx, check, (layout, dt, bits, arr, n, palette) = self.lib.vszip_image_unpack, self.ctx, self.check, self._image_unpack_args(srcs, planes, alphas, layout, src_bits, palette)
+        pal = palette.ctypes.data if palette is not None else None
+        return lambda: check(fn(ctx, layout, dt, bits, arr, n, pal))
 
     def upload_deband_tables(self, tab: dict) -> dict:
         """The tables of deband_tables() (or of the numpy spec) resident on the device, uploaded once per clip: `luma` / `chroma` as
