@@ -48,7 +48,10 @@ enum vszip_status {
 /* ---- context: one per (process, GPU); owns a stream and scratch ---------- */
 int vszip_ctx_create(int device, vszip_ctx **out);
 void vszip_ctx_destroy(vszip_ctx *ctx);
-/* Use an externally owned hipStream_t (passed as void*) instead of the context's own. */
+/* Use an externally owned hipStream_t (passed as void*) instead of the context's own; NULL is the null stream. Hand-over: everything
+ * the context queues on the new stream is ordered after everything it queued on its previous stream (the context's scratch, scalar
+ * buffers and tables are shared by consecutive calls) - the own stream is drained and destroyed, a caller's previous stream is joined
+ * with an event, so that stream must still exist at the time of this call. Work the CALLER queued on either stream is not ordered. */
 int vszip_ctx_set_stream(vszip_ctx *ctx, void *hip_stream);
 void *vszip_ctx_stream(vszip_ctx *ctx);
 int vszip_ctx_sync(vszip_ctx *ctx);
@@ -61,7 +64,8 @@ int vszip_ctx_set_staging(vszip_ctx *ctx, int mode);
 /* Options. Every switch of the library (vapoursynth-zip_amd/csrc/options.inc lists them with their defaults) is read from the
  * environment ONCE, when the context is created, under the name given here (e.g. "VSZIP_PLACEMENT", "VSZIP_STAGING",
  * "VSZIP_RT_NO_ICHAIN"); these two change / read one on a live context. Flags are 0 / 1. VSZIP_ERR_ARG: no such option;
- * VSZIP_ERR_UNSUPPORTED: a development variant that this build does not contain (-DVSZIP_DEV_VARIANTS). */
+ * VSZIP_ERR_UNSUPPORTED: a development variant that this build does not contain (-DVSZIP_DEV_VARIANTS).
+ * Read-only counters (get only): "VSZIP_STAT_MINMAX_PREDICTED", "VSZIP_STAT_MINMAX_FALLBACKS", "VSZIP_STAT_SCRATCH_KIB" (the context's scratch buffer, KiB). */
 int vszip_ctx_set_option(vszip_ctx *ctx, const char *name, int value);
 int vszip_ctx_get_option(vszip_ctx *ctx, const char *name, int *value);
 /* Error path of a caller that gives up on the current frame: drains the stream and forgets staged

@@ -42,6 +42,7 @@ struct vszip_ctx {
     hipStream_t stream = nullptr;
     bool own_stream = false;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    hipEvent_t handover = nullptr;  // vszip_ctx_set_stream: orders the new stream behind a caller's old one (created on first use)
     // second stream for kernels that run BESIDE the main stream's (EEDI3: the line kernel of the short planes next to the
     // vertical-consistency chains of the tall ones); its CU mask leaves `aux_reserved` CUs to the main stream, created on
     // first use; aux_fork / aux_join order the two

@@ -151,6 +151,10 @@ VSZIP_EXPORT int vszip_ctx_get_option(vszip_ctx *ctx, const char *name, int *val
         *value = ctx->minmax_fallbacks;
         return VSZIP_OK;
     }
+    if (strcmp(name, "VSZIP_STAT_SCRATCH_KIB") == 0) {  // the size of the shared scratch buffer (tests: a change means it was freed and reallocated)
+        *value = (int)(ctx->scratch_bytes >> 10);
+        return VSZIP_OK;
+    }
     for (const OptionDesc &d : kOptions)
         if (strcmp(d.env, name) == 0) {
             if (!d.field) return vszip_set_error(ctx, VSZIP_ERR_UNSUPPORTED, "%s is a development variant: build with -DVSZIP_DEV_VARIANTS", name);
@@ -248,6 +252,7 @@ VSZIP_EXPORT void vszip_ctx_destroy(vszip_ctx *ctx) {
     if (ctx->probe_ev1) (void)hipEventDestroy(ctx->probe_ev1);
     if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
     if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);
+    if (ctx->handover) (void)hipEventDestroy(ctx->handover);
     for (hipEvent_t e : ctx->probe_events) (void)hipEventDestroy(e);
     if (ctx->own_stream && ctx->stream) (void)hipStreamDestroy(ctx->stream);
     delete ctx;
@@ -255,11 +260,22 @@ VSZIP_EXPORT void vszip_ctx_destroy(vszip_ctx *ctx) {
 
 VSZIP_EXPORT int vszip_ctx_set_stream(vszip_ctx *ctx, void *hip_stream) {
     if (!ctx) return VSZIP_ERR_ARG;
+    (void)hipSetDevice(ctx->device);
+    hipStream_t next = (hipStream_t)hip_stream;
     if (ctx->own_stream && ctx->stream) {
         (void)hipStreamSynchronize(ctx->stream);
         (void)hipStreamDestroy(ctx->stream);
+    } else if (next != ctx->stream) {
+        // from one caller's stream to another: what the context queued on the old one may still be using the scratch buffer, the scalar buffers and
+        // the tables that the next call on the new one rewrites - the new stream waits for the old one's tail
+        bool ordered = (ctx->handover || hipEventCreateWithFlags(&ctx->handover, hipEventDisableTiming) == hipSuccess) &&
+                       hipEventRecord(ctx->handover, ctx->stream) == hipSuccess && hipStreamWaitEvent(next, ctx->handover, 0) == hipSuccess;
+        if (!ordered) {
+            (void)hipGetLastError();
+            if (hipDeviceSynchronize() != hipSuccess) return vszip_set_error(ctx, VSZIP_ERR_HIP, "vszip_ctx_set_stream: the previous stream could not be ordered before the new one");
+        }
     }
-    ctx->stream = (hipStream_t)hip_stream;
+    ctx->stream = next;
     ctx->own_stream = false;
     return VSZIP_OK;
 }
