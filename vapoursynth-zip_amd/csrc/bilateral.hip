@@ -1199,9 +1199,12 @@ int run_pbfic(vszip_ctx *ctx, const vszip_plane *planes, const vszip_bilateral_c
             floats += need;
         }
         a.n = n;
-        const int rc = vszip_ensure_scratch(ctx, floats * sizeof(float));
+        scratch::Layout lay;
+        const scratch::Region<float> wj = lay.take<float>(floats);  // every plane's layers, plane i's at wj_off
+        char *base;
+        const int rc = vszip_reserve_scratch(ctx, lay, &base);
         if (rc != VSZIP_OK) return rc;
-        a.wj = static_cast<float *>(ctx->scratch);
+        a.wj = wj.in(base);
         hipLaunchKernelGGL((pbfic_wj_kernel<T>), dim3((unsigned)blocks[0]), dim3(256), 0, ctx->stream, a);
         hipLaunchKernelGGL(pbfic_rg_h_kernel, dim3((unsigned)blocks[1]), dim3(64), 0, ctx->stream, a);
         hipLaunchKernelGGL(pbfic_rg_v_kernel, dim3((unsigned)blocks[2]), dim3(256), 0, ctx->stream, a);
@@ -1281,6 +1284,20 @@ int launch_lds16(vszip_ctx *ctx, BLParams prm, int blocks, bool joint, int max_r
     return joint ? launch_lds16_k<T, true, 0, 0>(ctx, prm, blocks, lds) : launch_lds16_k<T, false, 0, 0>(ctx, prm, blocks, lds);
 }
 
+// The walk kernels' strip counter, cleared, at the head of the scratch buffer
+int walk_counter(vszip_ctx *ctx, int **counter) {
+    scratch::Layout lay;
+    const scratch::Region<int> c = lay.take<int>(1);
+    lay.align_to(256);
+    lay.pad(256);  // the kernels' dummy store line, 256 B behind the counter
+    char *base;
+    const int rc = vszip_reserve_scratch(ctx, lay, &base);
+    if (rc != VSZIP_OK) return rc;
+    *counter = c.in(base);
+    VSZIP_HIP_CHECK(ctx, hipMemsetAsync(*counter, 0, sizeof(int), ctx->stream));
+    return VSZIP_OK;
+}
+
 // The column-walking kernel: strips of 64 - 2 CR output columns x kWalkBand rows; prm.p[i].block0 / nbx are re-based on strips.
 template <int CR, int CS, typename T = uint16_t>
 int launch_walk16(vszip_ctx *ctx, BLParams prm, int form) {  // form: 0 COARSE, 1 FINE, 2 PLATEAU (prm.lut_upper)
@@ -1292,10 +1309,9 @@ int launch_walk16(vszip_ctx *ctx, BLParams prm, int form) {  // form: 0 COARSE, 
         strips += p.nbx * ((p.h + kWalkBand - 1) / kWalkBand);
     }
     const int grid = std::min((strips + 15) / 16, 256);
-    int rcs = vszip_ensure_scratch(ctx, 512);  // the strip counter, and the dummy store line 256 B behind it
+    int *counter;
+    const int rcs = walk_counter(ctx, &counter);
     if (rcs != VSZIP_OK) return rcs;
-    int *counter = static_cast<int *>(ctx->scratch);
-    VSZIP_HIP_CHECK(ctx, hipMemsetAsync(counter, 0, sizeof(int), ctx->stream));
     vszip_probe_scope probe(ctx);
     if (form == 3)
         hipLaunchKernelGGL((bilateral_walk16_kernel<CR, CS, 3, T>), dim3(grid), dim3(1024), 0, ctx->stream, prm, strips, counter);
@@ -1321,10 +1337,9 @@ int launch_walk36(vszip_ctx *ctx, BLParams prm, int form) {
         strips += p.nbx * ((p.h + kWalkBand - 1) / kWalkBand);
     }
     const int grid = std::min((strips + 7) / 8, 256);
-    int rcs = vszip_ensure_scratch(ctx, 512);
+    int *counter;
+    const int rcs = walk_counter(ctx, &counter);
     if (rcs != VSZIP_OK) return rcs;
-    int *counter = static_cast<int *>(ctx->scratch);
-    VSZIP_HIP_CHECK(ctx, hipMemsetAsync(counter, 0, sizeof(int), ctx->stream));
     vszip_probe_scope probe(ctx);
     if (form == 3)
         hipLaunchKernelGGL((bilateral_walk36_kernel<3, T>), dim3(grid), dim3(512), 0, ctx->stream, prm, strips, counter);

@@ -1979,11 +1979,11 @@ int launch_fchain(vszip_ctx *ctx, const std::vector<RPlane> &pl, int radius, int
         });
 }
 
-// The banded integer vertical chain (boxblur_rt_ichain_kernel) in bands of band_rows rows (rt_plan::ichain_band_rows); kk_tab: room for ichain_table_bytes.
-size_t ichain_table_bytes(const std::vector<RPlane> &pl) {
+// The banded integer vertical chain (boxblur_rt_ichain_kernel) in bands of band_rows rows (rt_plan::ichain_band_rows); kk_tab: room for ichain_table_words.
+size_t ichain_table_words(const std::vector<RPlane> &pl) {
     size_t e = 0;
     for (const RPlane &q : pl) e += (size_t)((q.w + 63) & ~63) * kFcMaxPass;
-    return e * sizeof(uint32_t);
+    return e;
 }
 template <typename T>
 int launch_ichain_banded(vszip_ctx *ctx, const std::vector<RPlane> &pl, int radius, int npass, bool keep, int band_rows, uint32_t *kk_tab) {
@@ -2055,9 +2055,13 @@ int run_rt_fused(vszip_ctx *ctx, const vszip_plane *planes, int nplanes, int hra
         poff[i] = pe;
         pe += std::max((size_t)((planes[i].w + 63) & ~63) * planes[i].h, (size_t)((planes[i].h + 63) & ~63) * planes[i].w);
     }
-    int rc = vszip_ensure_scratch(ctx, 2 * pe * sizeof(T) + 256);
+    scratch::Layout lay;
+    const scratch::Region<T> set[2] = {lay.take<T>(pe), lay.take<T>(pe)};
+    lay.pad(256);  // dead tail
+    char *base;
+    int rc = vszip_reserve_scratch(ctx, lay, &base);
     if (rc != VSZIP_OK) return rc;
-    T *buf[2] = {static_cast<T *>(ctx->scratch), static_cast<T *>(ctx->scratch) + pe};
+    T *buf[2] = {set[0].in(base), set[1].in(base)};
     struct Cur { const void *ptr; int stride, w, h; };
     std::vector<Cur> cur(nplanes);
     for (int i = 0; i < nplanes; ++i) cur[i] = Cur{planes[i].src, (int)planes[i].src_stride, planes[i].w, planes[i].h};
@@ -2216,19 +2220,25 @@ int run_rt(vszip_ctx *ctx, const vszip_plane *planes, int nplanes, int hradius, 
         // then the banded chain's per-column constants
         bool banded = false;
         for (const rt_plan::Step &st : plan) banded = banded || st.kind == rt_plan::Kind::IntChainBanded;
-        const size_t planes_bytes = plan.size() > 1 ? (2 * elems * sizeof(T) + 255) & ~(size_t)255 : 0;
-        T *scratch[2] = {nullptr, nullptr};
+        const size_t set_elems = plan.size() > 1 ? elems : 0;
+        scratch::Layout lay;
+        const scratch::Region<T> set[2] = {lay.take<T>(set_elems), lay.take<T>(set_elems)};
+        lay.align_to(256);
+        const scratch::Region<uint32_t> kk = lay.take<uint32_t>(banded ? ichain_table_words(cur) : 0);
+        lay.pad(256);  // dead tail
+        T *plane_set[2] = {nullptr, nullptr};
         uint32_t *kk_tab = nullptr;
-        if (planes_bytes || banded) {
-            const int rc = vszip_ensure_scratch(ctx, planes_bytes + (banded ? ichain_table_bytes(cur) : 0) + 256);
+        if (set_elems || banded) {
+            char *base;
+            const int rc = vszip_reserve_scratch(ctx, lay, &base);
             if (rc != VSZIP_OK) return rc;
-            scratch[0] = static_cast<T *>(ctx->scratch);
-            scratch[1] = scratch[0] + elems;
-            kk_tab = reinterpret_cast<uint32_t *>(static_cast<char *>(ctx->scratch) + planes_bytes);
+            plane_set[0] = set[0].in(base);
+            plane_set[1] = set[1].in(base);
+            kk_tab = kk.in(base);
         }
         for (const rt_plan::Step &st : plan) {
             for (int i = 0; i < ng; ++i) {
-                cur[i].dst = st.to_dst ? planes[g0 + i].dst : static_cast<void *>(scratch[st.scratch] + goff[i]);
+                cur[i].dst = st.to_dst ? planes[g0 + i].dst : static_cast<void *>(plane_set[st.scratch] + goff[i]);
                 cur[i].dstride = st.to_dst ? (int)planes[g0 + i].dst_stride : rt_plan::scratch_pitch(cur[i].w);
             }
             const int rc = run_step<T>(ctx, cur, st, kk_tab);

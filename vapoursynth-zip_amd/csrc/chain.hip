@@ -10,26 +10,6 @@
 
 #include "common.hpp"
 
-static int ensure_chain_buf(vszip_ctx *ctx, size_t bytes) {
-    if (bytes <= ctx->chain_bytes) return VSZIP_OK;
-    if (ctx->chain_buf) {
-        VSZIP_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-        (void)hipFree(ctx->chain_buf);
-        ctx->chain_buf = nullptr;
-        ctx->chain_bytes = 0;
-    }
-    const size_t want = bytes + (bytes >> 3) + 4096;
-    if (vszip_hip_malloc(ctx, &ctx->chain_buf, want) != hipSuccess) return vszip_set_error(ctx, VSZIP_ERR_NOMEM, "chain buffer allocation of %zu bytes failed", want);
-    ctx->chain_bytes = want;
-    return VSZIP_OK;
-}
-
-void vszip_chain_release(vszip_ctx *ctx) {
-    if (ctx->chain_buf) (void)hipFree(ctx->chain_buf);
-    ctx->chain_buf = nullptr;
-    ctx->chain_bytes = 0;
-}
-
 VSZIP_EXPORT int vszip_chain_run(vszip_ctx *ctx, int dtype, const vszip_chain_stage *stages, int nstages, const vszip_plane *planes, const int *plane_slot, int nplanes) {
     if (!ctx || !stages || !planes || !plane_slot || nstages <= 0 || nplanes <= 0) return VSZIP_ERR_ARG;
     const int bps = vszip_dtype_size(dtype);
@@ -46,9 +26,9 @@ VSZIP_EXPORT int vszip_chain_run(vszip_ctx *ctx, int dtype, const vszip_chain_st
         pitch[i] = ((size_t)planes[i].w * bps + 255) & ~(size_t)255;
         off[i + 1] = off[i] + (writers[i] > 1 ? 2 * pitch[i] * planes[i].h : 0);
     }
-    int rc = ensure_chain_buf(ctx, off[nplanes]);
+    int rc = vszip_reserve(ctx, ctx->chain_buf, off[nplanes], vszip_scratch_want(off[nplanes]), "chain buffer");
     if (rc != VSZIP_OK) return rc;
-    char *buf = static_cast<char *>(ctx->chain_buf);
+    char *buf = static_cast<char *>(ctx->chain_buf.ptr);
     std::vector<const void *> cur(nplanes);
     std::vector<ptrdiff_t> cur_stride(nplanes);
     std::vector<int> written(nplanes, 0);

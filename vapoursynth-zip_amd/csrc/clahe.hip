@@ -329,8 +329,10 @@ int run(vszip_ctx *ctx, const vszip_plane *planes, int nplanes, uint32_t limit, 
     const size_t hbytes = (size_t)tiles_x * tiles_y * HS * 4, lbytes = (size_t)tiles_x * tiles_y * HS * sizeof(T);
     const int per_group = (int)std::max<size_t>(1, std::min<size_t>(CParams::capacity, cap / (hbytes + lbytes)));
     const int gmax = std::min(per_group, nplanes);
-    const size_t need = (hbytes + lbytes) * (size_t)gmax;  // [histograms of the group][LUTs of the group]
-    int rc = vszip_ensure_scratch(ctx, need);
+    scratch::Layout lay;  // [histograms of the group][LUTs of the group]
+    const scratch::Region<char> hist = lay.take<char>(hbytes * gmax), lut = lay.take<char>(lbytes * gmax);
+    char *base;
+    int rc = vszip_reserve_scratch(ctx, lay, &base);
     if (rc != VSZIP_OK) return rc;
 
     for (int done = 0; done < nplanes;) {
@@ -342,8 +344,8 @@ int run(vszip_ctx *ctx, const vszip_plane *planes, int nplanes, uint32_t limit, 
             CPlane &d = prm.p[n];
             d.src = s.src;
             d.dst = s.dst;
-            d.hist = reinterpret_cast<uint32_t *>(static_cast<char *>(ctx->scratch) + hbytes * n);
-            d.lut = static_cast<char *>(ctx->scratch) + hbytes * gmax + lbytes * n;
+            d.hist = reinterpret_cast<uint32_t *>(hist.in(base) + hbytes * n);
+            d.lut = lut.in(base) + lbytes * n;
             grp += hbytes;
             d.sstride = (int)s.src_stride;
             d.dstride = (int)s.dst_stride;
@@ -381,7 +383,7 @@ int run(vszip_ctx *ctx, const vszip_plane *planes, int nplanes, uint32_t limit, 
             d.lds = (size_t)band_trows * tiles_x * 256 <= (size_t)kLdsLutBytes;
         }
         prm.nplanes = n;
-        VSZIP_HIP_CHECK(ctx, hipMemsetAsync(ctx->scratch, 0, grp, ctx->stream));
+        VSZIP_HIP_CHECK(ctx, hipMemsetAsync(hist.in(base), 0, grp, ctx->stream));
         {
             vszip_probe_scope probe(ctx);
             hipLaunchKernelGGL((clahe_hist_kernel<T>), dim3(hb), dim3(kHistThreads), 0, ctx->stream, prm);

@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../../include/vszip_hip.h"
+#include "scratch_layout.hpp"
 
 #define VSZIP_EXPORT extern "C" __attribute__((visibility("default")))
 
@@ -35,6 +36,12 @@ struct vszip_options {
 #undef VSZIP_DEV_OPT
 };
 
+// A grow-only device buffer of a context: vszip_reserve / vszip_release (ctx.hip) are all that allocate and free one.
+struct vszip_devbuf {
+    void *ptr = nullptr;
+    size_t bytes = 0;
+};
+
 struct vszip_ctx {
     vszip_options opt;
     int device = 0;
@@ -53,11 +60,9 @@ struct vszip_ctx {
     hipStream_t side_stream = nullptr;
     hipEvent_t side_fork = nullptr, side_join = nullptr;
     std::string err;
-    // grow-only device scratch (filters that need intermediates) and a small
-    // pinned + device pair for returning scalars
-    void *scratch = nullptr;
-    size_t scratch_bytes = 0;
-    void *scalars_dev = nullptr;
+    // device scratch (filters that need intermediates: vszip_reserve_scratch) and a small
+    // pinned host buffer, device-visible, for returning scalars
+    vszip_devbuf scratch;
     void *scalars_host = nullptr;
     size_t scalars_bytes = 0;
     // dominant-kernel probe (vszip_probe_*): HIP event pairs recorded on `stream` around the
@@ -66,8 +71,7 @@ struct vszip_ctx {
     std::vector<hipEvent_t> probe_events;  // begin/end pairs
     size_t probe_used = 0;
     // XPSNR block sums: a buffer of its own that the weighting kernel leaves zeroed for the next call
-    void *xpsnr_sums = nullptr;
-    size_t xpsnr_sums_bytes = 0;
+    vszip_devbuf xpsnr_sums;
     bool xpsnr_clean = false;
     // Host staging (vszip_ctx_set_staging): 0 = copy straight from/to the caller's pointers (pinned
     // callers, or pageable memory that the runtime pins in place), 1 = through this context's pinned
@@ -84,27 +88,29 @@ struct vszip_ctx {
     std::vector<PendingOut> pending_out;
     // thresholded PlaneMinMax on 16-bit / float planes: where the previous call's answers lay, per plane (device, [planes][2] words), and what that
     // call looked like — a call of the same shape (the next frames of a clip) looks there first and reads its planes once (planestats.hip)
-    void *minmax_pred = nullptr;
-    size_t minmax_pred_planes = 0;
+    vszip_devbuf minmax_pred;  // (the one buffer whose contents survive its growth: planestats.hip copies them across)
     std::vector<uint64_t> minmax_sig;   // per plane group of a call, kPredSlots entries: signatures of the thresholded calls that left predictions (0: none)
     std::vector<uint64_t> minmax_used;  // ... and when each was last used (minmax_tick)
     uint64_t minmax_tick = 0;
     int minmax_predicted = 0;  // plane groups of thresholded calls that ran the single predicted sweep ("VSZIP_STAT_MINMAX_PREDICTED": read-only)
     int minmax_fallbacks = 0;  // synchronous predicted calls whose flags asked for the two sweeps (vszip_ctx_get_option "VSZIP_STAT_MINMAX_FALLBACKS": read-only)
-    void *chain_buf = nullptr;  // vszip_chain_run: intermediate planes (grow-only)
-    size_t chain_bytes = 0;
+    vszip_devbuf chain_buf;  // vszip_chain_run: intermediate planes
     void *ssim_lut = nullptr;  // SSIMULACRA2 colour pre-stage: cached conversion table (ssimulacra2.hip)
     int &scan_mode = opt.scan_mode;  // BoxBlur CT: 0 = ring kernel (DPP scan), 1 = generic kernel + shuffle scan, 2 = generic kernel + DPP scan
     hipEvent_t probe_ev0 = nullptr, probe_ev1 = nullptr;  // vszip_dev_probe_region's own timing events
 };
 
 int vszip_set_error(vszip_ctx *ctx, int code, const char *fmt, ...);
-int vszip_ensure_scratch(vszip_ctx *ctx, size_t bytes);
 hipError_t vszip_hip_malloc(vszip_ctx *ctx, void **p, size_t bytes);  // the library's internal allocations (plain hipMalloc)
-int vszip_ensure_scalars(vszip_ctx *ctx, size_t bytes);
+// need <= buf.bytes: nothing. Else the stream is drained, the old allocation freed and `want` (>= need: the caller's growth policy) bytes allocated;
+// *grew tells a caller that keeps state in the buffer. VSZIP_ERR_NOMEM ("<what> ...") leaves the buffer empty.
+int vszip_reserve(vszip_ctx *ctx, vszip_devbuf &buf, size_t need, size_t want, const char *what, bool *grew = nullptr);
+void vszip_release(vszip_devbuf &buf);
+inline size_t vszip_scratch_want(size_t need) { return need + (need >> 3) + 4096; }  // growth of the scratch and the chain buffer
+int vszip_reserve_scratch(vszip_ctx *ctx, const scratch::Layout &layout, char **base);  // ctx->scratch for a filter's layout
+int vszip_ensure_scalars(vszip_ctx *ctx, size_t bytes);  // ctx->scalars_host (contents are not kept)
 void vszip_ssim_release(vszip_ctx *ctx);  // frees ctx->ssim_lut
-void vszip_chain_release(vszip_ctx *ctx);  // frees ctx->chain_buf
-void vszip_planestats_release(vszip_ctx *ctx);  // frees ctx->minmax_pred
+void vszip_planestats_release(vszip_ctx *ctx);  // forgets what ctx->minmax_pred held
 void vszip_bilateral_forget_lut(const void *dptr);  // vszip_dev_free: a packed range LUT goes with its allocation
 // Bracket the launch of a filter's dominant kernel; no-ops unless the probe is enabled.
 void vszip_probe_mark(vszip_ctx *ctx);
@@ -122,6 +128,13 @@ struct vszip_probe_scope {
         if (e_ != hipSuccess)                                                                   \
             return vszip_set_error((ctx), VSZIP_ERR_HIP, "%s failed: %s", #call, hipGetErrorString(e_)); \
     } while (0)
+
+// the pinned scalars buffer as the kernels see it
+template <typename T>
+int vszip_scalars_dev(vszip_ctx *ctx, T **dev) {
+    VSZIP_HIP_CHECK(ctx, hipHostGetDevicePointer(reinterpret_cast<void **>(dev), ctx->scalars_host, 0));
+    return VSZIP_OK;
+}
 
 static inline int vszip_dtype_size(int dt) {
     switch (dt) {

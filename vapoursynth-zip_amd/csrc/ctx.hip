@@ -26,32 +26,47 @@ int vszip_set_error(vszip_ctx *ctx, int code, const char *fmt, ...) {
     return code;
 }
 
-int vszip_ensure_scratch(vszip_ctx *ctx, size_t bytes) {
-    if (bytes <= ctx->scratch_bytes) return VSZIP_OK;
-    if (ctx->scratch) {
+int vszip_reserve(vszip_ctx *ctx, vszip_devbuf &buf, size_t need, size_t want, const char *what, bool *grew) {
+    if (grew) *grew = false;
+    if (need <= buf.bytes) return VSZIP_OK;
+    if (buf.ptr) {  // what is queued may still use it
         VSZIP_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-        VSZIP_HIP_CHECK(ctx, hipFree(ctx->scratch));
-        ctx->scratch = nullptr;
-        ctx->scratch_bytes = 0;
+        VSZIP_HIP_CHECK(ctx, hipFree(buf.ptr));
+        buf = vszip_devbuf();
     }
-    const size_t want = bytes + (bytes >> 3) + 4096;
-    if (vszip_hip_malloc(ctx, &ctx->scratch, want) != hipSuccess) return vszip_set_error(ctx, VSZIP_ERR_NOMEM, "scratch allocation of %zu bytes failed", want);
-    ctx->scratch_bytes = want;
+    if (vszip_hip_malloc(ctx, &buf.ptr, want) != hipSuccess) {
+        buf = vszip_devbuf();
+        return vszip_set_error(ctx, VSZIP_ERR_NOMEM, "%s allocation of %zu bytes failed", what, want);
+    }
+    buf.bytes = want;
+    if (grew) *grew = true;
     return VSZIP_OK;
+}
+
+void vszip_release(vszip_devbuf &buf) {
+    if (buf.ptr) (void)hipFree(buf.ptr);
+    buf = vszip_devbuf();
+}
+
+int vszip_reserve_scratch(vszip_ctx *ctx, const scratch::Layout &layout, char **base) {
+    const int rc = vszip_reserve(ctx, ctx->scratch, layout.bytes(), vszip_scratch_want(layout.bytes()), "scratch");
+    *base = static_cast<char *>(ctx->scratch.ptr);
+    return rc;
 }
 
 int vszip_ensure_scalars(vszip_ctx *ctx, size_t bytes) {
     if (bytes <= ctx->scalars_bytes) return VSZIP_OK;
-    if (ctx->scalars_dev) {
+    if (ctx->scalars_host) {
         VSZIP_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-        (void)hipFree(ctx->scalars_dev);
         (void)hipHostFree(ctx->scalars_host);
-        ctx->scalars_dev = ctx->scalars_host = nullptr;
+        ctx->scalars_host = nullptr;
         ctx->scalars_bytes = 0;
     }
     const size_t want = (bytes + 4095) & ~(size_t)4095;
-    if (vszip_hip_malloc(ctx, &ctx->scalars_dev, want) != hipSuccess) return vszip_set_error(ctx, VSZIP_ERR_NOMEM, "scalar buffer allocation failed");
-    if (hipHostMalloc(&ctx->scalars_host, want, hipHostMallocDefault) != hipSuccess) return vszip_set_error(ctx, VSZIP_ERR_NOMEM, "pinned scalar buffer allocation failed");
+    if (hipHostMalloc(&ctx->scalars_host, want, hipHostMallocDefault) != hipSuccess) {
+        ctx->scalars_host = nullptr;
+        return vszip_set_error(ctx, VSZIP_ERR_NOMEM, "pinned scalar buffer allocation of %zu bytes failed", want);
+    }
     ctx->scalars_bytes = want;
     return VSZIP_OK;
 }
@@ -152,7 +167,7 @@ VSZIP_EXPORT int vszip_ctx_get_option(vszip_ctx *ctx, const char *name, int *val
         return VSZIP_OK;
     }
     if (strcmp(name, "VSZIP_STAT_SCRATCH_KIB") == 0) {  // the size of the shared scratch buffer (tests: a change means it was freed and reallocated)
-        *value = (int)(ctx->scratch_bytes >> 10);
+        *value = (int)(ctx->scratch.bytes >> 10);
         return VSZIP_OK;
     }
     for (const OptionDesc &d : kOptions)
@@ -227,12 +242,9 @@ VSZIP_EXPORT void vszip_ctx_destroy(vszip_ctx *ctx) {
     if (!ctx) return;
     (void)hipSetDevice(ctx->device);
     (void)hipStreamSynchronize(ctx->stream);
-    if (ctx->scratch) (void)hipFree(ctx->scratch);
-    if (ctx->xpsnr_sums) (void)hipFree(ctx->xpsnr_sums);
+    for (vszip_devbuf *b : {&ctx->scratch, &ctx->xpsnr_sums, &ctx->chain_buf, &ctx->minmax_pred}) vszip_release(*b);
     vszip_ssim_release(ctx);
-    vszip_chain_release(ctx);
     vszip_planestats_release(ctx);
-    if (ctx->scalars_dev) (void)hipFree(ctx->scalars_dev);
     if (ctx->scalars_host) (void)hipHostFree(ctx->scalars_host);
     if (ctx->stage) (void)hipHostFree(ctx->stage);
     vszip_aux_forget(ctx);

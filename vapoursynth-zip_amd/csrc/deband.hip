@@ -136,19 +136,23 @@ VSZIP_EXPORT int vszip_deband(vszip_ctx *ctx, int dtype, const vszip_plane *plan
     prm.blur_first = blur_first != 0;
     for (int done = 0; done < nplanes;) {
         int n = nplanes - done;
-        size_t need = 0;
+        scratch::Layout lay;
+        std::vector<scratch::Region<float>> angle;  // the group's angle planes, a multiple of 256 bytes each
+        char *base = nullptr;
         if (sample_mode == 7) {
             n = 0;
             while (done + n < nplanes) {
-                const size_t bytes = ((size_t)planes[done + n].w * planes[done + n].h * sizeof(float) + 255) & ~(size_t)255;
-                if (n > 0 && need + bytes > cap) break;
-                need += bytes;
+                scratch::Layout with = lay;
+                const scratch::Region<float> a = with.take<float>((size_t)planes[done + n].w * planes[done + n].h);
+                with.align_to(256);
+                if (n > 0 && with.bytes() > cap) break;
+                lay = with;
+                angle.push_back(a);
                 ++n;
             }
-            const int rc = vszip_ensure_scratch(ctx, need);
+            const int rc = vszip_reserve_scratch(ctx, lay, &base);
             if (rc != VSZIP_OK) return rc;
         }
-        size_t used = 0;
         const int rc = vszip_for_each_table(
             ctx, prm, n,
             [&](DebPlane &d, int j) -> int {
@@ -160,10 +164,7 @@ VSZIP_EXPORT int vszip_deband(vszip_ctx *ctx, int dtype, const vszip_plane *plan
                 d.off = q.offsets;
                 d.grain = q.grain;
                 d.angle = nullptr;
-                if (sample_mode == 7) {
-                    d.angle = reinterpret_cast<const float *>(static_cast<const char *>(ctx->scratch) + used);
-                    used += ((size_t)s.w * s.h * sizeof(float) + 255) & ~(size_t)255;
-                }
+                if (sample_mode == 7) d.angle = angle[j].in(base);
                 d.sstride = (int)s.src_stride;
                 d.dstride = (int)s.dst_stride;
                 d.ostride = (int)q.offsets_pitch;

@@ -1815,13 +1815,9 @@ static int eedi3_batch(vszip_ctx *ctx, const vszip_plane *planes, const float *c
     const int tpitch = hp ? 4 * up->mdis + 1 : (masked20 ? 2 * 20 + 1 : 2 * up->mdis + 1);
 
     // geometry of the vertical pipeline per plane (EEDI3H runs it on the transposed plane)
-    struct Geo {
-        int L, n_src, n_dst, n_interp;
-        size_t srcT, dstT, scT;  // float offsets into scratch (horizontal only)
-        size_t mT;               // byte offset of the transposed mask (horizontal only)
-    };
+    using Geo = scratch::Eedi3Plane;
     std::vector<Geo> geo(nplanes);
-    size_t fl = 0, lines = 0, pb = 0, dm = 0, mb = 0;
+    size_t lines = 0;
     for (int i = 0; i < nplanes; ++i) {
         const vszip_plane &s = planes[i];
         if (!s.src || !s.dst || s.w <= 0 || s.h <= 0) return vszip_set_error(ctx, VSZIP_ERR_ARG, "%s: bad plane %d", name, i);
@@ -1838,36 +1834,29 @@ static int eedi3_batch(vszip_ctx *ctx, const vszip_plane *planes, const float *c
         if (g.L < up->nrad + 2)
             return vszip_set_error(ctx, VSZIP_ERR_UNSUPPORTED, "%s: lines of %d samples are shorter than nrad+2 = %d; the reference's padded rows are undefined there", name, g.L,
                                    up->nrad + 2);
-        if (horizontal) {
-            g.srcT = fl;
-            fl += (size_t)g.n_src * g.L;
-            g.dstT = fl;
-            fl += (size_t)g.n_dst * g.L;
-            g.scT = fl;
-            if (up->vcheck > 0 && sclips && sclips[i]) fl += (size_t)g.n_dst * g.L;
-            g.mT = mb;
-            if (mclips && mclips[i]) mb += (((size_t)g.n_src * g.L) + 255) & ~(size_t)255;
-        }
+        g.sclip = sclips && sclips[i];
+        g.mclip = mclips && mclips[i];
         lines += g.n_interp;
-        pb += (size_t)g.n_interp * ((g.L + kXB - 1) / kXB * kXB) * tpitch;  // the line kernel stores whole 64-column blocks
-        dm += (size_t)g.n_interp * g.L;
     }
-    size_t bytes = (fl * sizeof(float) + dm * sizeof(int) + pb + mb + 4096 + 255) & ~(size_t)255;
-    const size_t gline_off = bytes;  // vcheck on lines wider than 8192: two lines per plane
+    // Plane slots: the tall planes of the call first (the luma planes of a subsampled clip). The vertical-consistency
+    // pass is a sequential chain per plane, as long as the plane is tall and busy on one CU per plane only; with the
+    // tall planes' lines interpolated first their chains run on a second stream BESIDE the line kernel of the short
+    // planes, and only the short planes' (half as long) chains remain after it.
+    std::vector<int> order(nplanes);
+    int ntall = 0, lines_tall = 0;
     {
-        int maxL = 0;
-        for (int i = 0; i < nplanes; ++i) maxL = std::max(maxL, geo[i].L);
-        if (up->vcheck > 0 && maxL > 8192) bytes += (size_t)nplanes * 2 * ((maxL + 63) & ~63) * sizeof(float);
+        int max_interp = 0;
+        for (int i = 0; i < nplanes; ++i) max_interp = std::max(max_interp, geo[i].n_interp);
+        for (int i = 0; i < nplanes; ++i)
+            if (4 * geo[i].n_interp >= 3 * max_interp) order[ntall++] = i;
+        int k = ntall;
+        for (int i = 0; i < nplanes; ++i)
+            if (4 * geo[i].n_interp < 3 * max_interp) order[k++] = i;
     }
-    int rc = vszip_ensure_scratch(ctx, bytes);
+    const scratch::Eedi3Scratch lay = scratch::eedi3_scratch(geo.data(), order.data(), nplanes, horizontal != 0, up->vcheck > 0, tpitch, kXB);
+    char *base;
+    int rc = vszip_reserve_scratch(ctx, lay.all, &base);
     if (rc != VSZIP_OK) return rc;
-    char *base = static_cast<char *>(ctx->scratch);
-    float *fbase = reinterpret_cast<float *>(base);
-    int *dbase = reinterpret_cast<int *>(base + fl * sizeof(float));
-    // the back-pointer area is written with 16-byte stores: keep it 256-byte aligned (the +4096 of `bytes` covers the padding)
-    const size_t pb_off = (fl * sizeof(float) + dm * sizeof(int) + 255) & ~(size_t)255;
-    int8_t *pbase = reinterpret_cast<int8_t *>(base + pb_off);
-    uint8_t *mbase = reinterpret_cast<uint8_t *>(base + pb_off + pb);
     GExtra gx;
     gx.hp = hp;
 
@@ -1892,41 +1881,26 @@ static int eedi3_batch(vszip_ctx *ctx, const vszip_plane *planes, const float *c
     vp.rcp0 = 1.0f / vt0;
     vp.rcp1 = 1.0f / vt1;
     vp.rcp2 = 1.0f / up->vthresh2;
-    size_t dmo = 0, pbo = 0;
     int line0 = 0, maxw = 0, maxsrc = 0;
     const dim3 tb(kTT, 8);
-    // Plane slots: the tall planes of the call first (the luma planes of a subsampled clip). The vertical-consistency
-    // pass is a sequential chain per plane, as long as the plane is tall and busy on one CU per plane only; with the
-    // tall planes' lines interpolated first their chains run on a second stream BESIDE the line kernel of the short
-    // planes, and only the short planes' (half as long) chains remain after it.
-    std::vector<int> order(nplanes);
-    int ntall = 0, lines_tall = 0;
-    {
-        int max_interp = 0;
-        for (int i = 0; i < nplanes; ++i) max_interp = std::max(max_interp, geo[i].n_interp);
-        for (int i = 0; i < nplanes; ++i)
-            if (4 * geo[i].n_interp >= 3 * max_interp) order[ntall++] = i;
-        int k = ntall;
-        for (int i = 0; i < nplanes; ++i)
-            if (4 * geo[i].n_interp < 3 * max_interp) order[k++] = i;
-    }
     for (int slot = 0; slot < nplanes; ++slot) {
         const int i = order[slot];
         const vszip_plane &s = planes[i];
         const Geo &g = geo[i];
+        const scratch::Eedi3PlaneScratch &gs = lay.p[i];
         EPlane &d = ep.p[slot];
         if (slot == ntall) lines_tall = line0;
         if (horizontal) {
-            float *srcT = fbase + g.srcT;
+            float *srcT = gs.srcT.in(base);
             hipLaunchKernelGGL(transpose_kernel, dim3((s.w + kTT - 1) / kTT, (s.h + kTT - 1) / kTT), tb, 0, ctx->stream, static_cast<const float *>(s.src), srcT,
                                (int)s.src_stride, g.L, s.w, s.h);
             d.src = srcT;
-            d.dst = fbase + g.dstT;
+            d.dst = gs.dstT.in(base);
             d.sstride = d.dstride = g.L;
             vp.scp[slot] = nullptr;
             vp.scstride[slot] = g.L;
             if (up->vcheck > 0 && sclips && sclips[i]) {
-                float *scT = fbase + g.scT;
+                float *scT = gs.scT.in(base);
                 hipLaunchKernelGGL(transpose_kernel, dim3((g.n_dst + kTT - 1) / kTT, (s.h + kTT - 1) / kTT), tb, 0, ctx->stream, sclips[i], scT,
                                    (int)sclip_strides[i], g.L, g.n_dst, s.h);
                 vp.scp[slot] = scT;
@@ -1934,7 +1908,7 @@ static int eedi3_batch(vszip_ctx *ctx, const vszip_plane *planes, const float *c
             gx.mask[slot] = nullptr;
             gx.mstride[slot] = g.L;
             if (mclips && mclips[i]) {  // mask has the source plane's geometry (w x h) -> transposed: w lines of h
-                uint8_t *mT = mbase + g.mT;
+                uint8_t *mT = gs.maskT.in(base);
                 hipLaunchKernelGGL(transpose_u8_kernel, dim3((s.w + kTT - 1) / kTT, (s.h + kTT - 1) / kTT), tb, 0, ctx->stream, mclips[i], mT, (int)mclip_strides[i], g.L,
                                    s.w, s.h);
                 gx.mask[slot] = mT;
@@ -1953,11 +1927,9 @@ static int eedi3_batch(vszip_ctx *ctx, const vszip_plane *planes, const float *c
         d.n_src = g.n_src;
         d.n_dst = g.n_dst;
         d.n_interp = g.n_interp;
-        d.dmap = dbase + dmo;
-        d.pback = pbase + pbo;
+        d.dmap = gs.dmap.in(base);
+        d.pback = gs.pback.in(base);
         d.line0 = line0;
-        dmo += (size_t)g.n_interp * g.L;
-        pbo += (size_t)g.n_interp * ((g.L + kXB - 1) / kXB * kXB) * tpitch;
         line0 += g.n_interp;
         maxw = std::max(maxw, g.L);
         maxsrc = std::max(maxsrc, g.n_src);
@@ -1970,7 +1942,7 @@ static int eedi3_batch(vszip_ctx *ctx, const vszip_plane *planes, const float *c
     for (int i = 0; i < nplanes; ++i) maxL = std::max(maxL, geo[i].L);
     vp.gline = nullptr;
     vp.gline_pitch = (maxL + 63) & ~63;
-    if (maxL > 8192) vp.gline = reinterpret_cast<float *>(base + gline_off);
+    if (maxL > 8192) vp.gline = lay.gline.in(base);
     const bool vc_lds = up->vcheck > 0 && maxL <= kVcLdsMaxL && !ctx->opt.vcheck_global;
     auto launch_vcheck_lds = [&](hipStream_t st, int first, int count) {
         int gl = 0;  // the widest line of THIS launch (the short planes of a 4K 4:2:0 clip are 1920 wide: two columns a thread, not the luma's four)
@@ -2141,7 +2113,7 @@ static int eedi3_batch(vszip_ctx *ctx, const vszip_plane *planes, const float *c
             const vszip_plane &s = planes[i];
             const Geo &g = geo[i];
             // dstT is n_dst lines of L -> dst is L (= src_h) rows of n_dst columns
-            hipLaunchKernelGGL(transpose_kernel, dim3((g.L + kTT - 1) / kTT, (g.n_dst + kTT - 1) / kTT), tb, 0, ctx->stream, fbase + g.dstT, static_cast<float *>(s.dst), g.L,
+            hipLaunchKernelGGL(transpose_kernel, dim3((g.L + kTT - 1) / kTT, (g.n_dst + kTT - 1) / kTT), tb, 0, ctx->stream, lay.p[i].dstT.in(base), static_cast<float *>(s.dst), g.L,
                                (int)s.dst_stride, g.L, g.n_dst);
         }
         VSZIP_HIP_CHECK(ctx, hipGetLastError());

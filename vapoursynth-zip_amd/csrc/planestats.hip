@@ -1010,6 +1010,7 @@ __global__ __launch_bounds__(kSweepThreads) void hist_sweep_kernel(const PSParam
 struct Launch {
     PSParams prm;
     int total_blocks = 0;
+    size_t clear_bytes = 0;  // hist, bucket and shist are contiguous: one memset from prm.hist
 };
 
 int prepare(vszip_ctx *ctx, const vszip_plane *planes, int nplanes, bool need_ref, Launch &L, double *result_dev) {
@@ -1039,22 +1040,19 @@ int prepare(vszip_ctx *ctx, const vszip_plane *planes, int nplanes, bool need_re
     }
     L.total_blocks = blocks;
     VSZIP_HIP_CHECK(ctx, hipSetDevice(ctx->device));
-    const size_t need = (size_t)blocks * 4 * sizeof(double) + (size_t)nplanes * (kHistWords + kBucketWords + 256) * sizeof(uint32_t) + (size_t)nplanes * 4 * sizeof(double) + 256;
-    int rc = vszip_ensure_scratch(ctx, need);
+    const scratch::PlaneStatsScratch lay = scratch::planestats_scratch((size_t)blocks, (size_t)nplanes, kHistWords, kBucketWords);
+    char *base;
+    int rc = vszip_reserve_scratch(ctx, lay.all, &base);
     if (rc != VSZIP_OK) return rc;
-    char *p = static_cast<char *>(ctx->scratch);
-    prm.partial = reinterpret_cast<double *>(p);
-    p += (size_t)blocks * 4 * sizeof(double);
-    p += (size_t)nplanes * 4 * sizeof(double);
+    prm.partial = lay.partial.in(base);
     // the final kernels write the per-plane results ([plane][4] doubles) straight into pinned host memory (device-visible):
     // the context's own buffer (the calls that return values: one synchronise at the end, no copy command) or the caller's
     // (the _async calls: no synchronise at all)
     prm.result = result_dev;
-    prm.hist = reinterpret_cast<uint32_t *>(p);
-    p += (size_t)nplanes * kHistWords * sizeof(uint32_t);
-    prm.bucket = reinterpret_cast<uint32_t *>(p);
-    p += (size_t)nplanes * kBucketWords * sizeof(uint32_t);
-    prm.shist = reinterpret_cast<uint32_t *>(p);
+    prm.hist = lay.hist.in(base);
+    prm.bucket = lay.bucket.in(base);
+    prm.shist = lay.shist.in(base);
+    L.clear_bytes = lay.clear_bytes();
     prm.pred = nullptr;
     return VSZIP_OK;
 }
@@ -1064,8 +1062,7 @@ int result_buffer(vszip_ctx *ctx, int nplanes, double **host, double **dev) {
     const int rc = vszip_ensure_scalars(ctx, (size_t)nplanes * 4 * sizeof(double));
     if (rc != VSZIP_OK) return rc;
     *host = static_cast<double *>(ctx->scalars_host);
-    VSZIP_HIP_CHECK(ctx, hipHostGetDevicePointer(reinterpret_cast<void **>(dev), ctx->scalars_host, 0));
-    return VSZIP_OK;
+    return vszip_scalars_dev(ctx, dev);
 }
 // a caller's pinned array as the kernels see it
 int caller_buffer(vszip_ctx *ctx, double *pinned, double **dev) {
@@ -1160,17 +1157,15 @@ int run_minmax_t(vszip_ctx *ctx, Launch &L, bool no_thr, int batch, std::functio
         // kPredSlots tables per plane group, by signature, least recently used replaced: the thresholded statistics of several clips (or one clip under
         // several thresholds) of a filter graph arrive interleaved on one context, and each keeps its own predictions
         const size_t group = (size_t)batch * kPredSlots, need = (group + kPredSlots) * kPlanesPerLaunch;
-        if (ctx->minmax_pred_planes < need) {  // grow-only, old predictions kept (a group's tables do not move when later groups are added)
-            const size_t cap = std::max<size_t>(need, 2 * ctx->minmax_pred_planes);
+        constexpr size_t kPlaneBytes = 2 * sizeof(uint32_t);
+        if (ctx->minmax_pred.bytes < need * kPlaneBytes) {  // grow-only, old predictions kept (a group's tables do not move when later groups are added): copy and swap
+            const size_t cap = std::max<size_t>(need * kPlaneBytes, 2 * ctx->minmax_pred.bytes);
             void *np = nullptr;
             VSZIP_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-            if (vszip_hip_malloc(ctx, &np, cap * 2 * sizeof(uint32_t)) != hipSuccess) return vszip_set_error(ctx, VSZIP_ERR_NOMEM, "PlaneMinMax: prediction table allocation failed");
-            if (ctx->minmax_pred) {
-                VSZIP_HIP_CHECK(ctx, hipMemcpy(np, ctx->minmax_pred, ctx->minmax_pred_planes * 2 * sizeof(uint32_t), hipMemcpyDeviceToDevice));
-                (void)hipFree(ctx->minmax_pred);
-            }
-            ctx->minmax_pred = np;
-            ctx->minmax_pred_planes = cap;
+            if (vszip_hip_malloc(ctx, &np, cap) != hipSuccess) return vszip_set_error(ctx, VSZIP_ERR_NOMEM, "PlaneMinMax: prediction table allocation of %zu bytes failed", cap);
+            if (ctx->minmax_pred.ptr) VSZIP_HIP_CHECK(ctx, hipMemcpy(np, ctx->minmax_pred.ptr, ctx->minmax_pred.bytes, hipMemcpyDeviceToDevice));
+            vszip_release(ctx->minmax_pred);
+            ctx->minmax_pred = {np, cap};
         }
         if (ctx->minmax_sig.size() < group + kPredSlots) {
             ctx->minmax_sig.resize(group + kPredSlots, 0);
@@ -1188,7 +1183,7 @@ int run_minmax_t(vszip_ctx *ctx, Launch &L, bool no_thr, int batch, std::functio
         }
         ctx->minmax_sig[slot] = sig;  // (this call leaves predictions for the next one of its signature, whichever way it runs)
         ctx->minmax_used[slot] = ++ctx->minmax_tick;
-        L.prm.pred = static_cast<uint32_t *>(ctx->minmax_pred) + slot * kPlanesPerLaunch * 2;
+        L.prm.pred = static_cast<uint32_t *>(ctx->minmax_pred.ptr) + slot * kPlanesPerLaunch * 2;
         if (predicted) ++ctx->minmax_predicted;
     } else {
         L.prm.pred = nullptr;
@@ -1200,8 +1195,7 @@ int run_minmax_t(vszip_ctx *ctx, Launch &L, bool no_thr, int batch, std::functio
         }
         hipLaunchKernelGGL(minmax_final_kernel, dim3(L.prm.nplanes), dim3(64), 0, ctx->stream, L.prm, is_int);
     } else {
-        // hist, bucket and shist are contiguous: one memset
-        VSZIP_HIP_CHECK(ctx, hipMemsetAsync(L.prm.hist, 0, (size_t)L.prm.nplanes * (kHistWords + kBucketWords + 256) * sizeof(uint32_t), ctx->stream));
+        VSZIP_HIP_CHECK(ctx, hipMemsetAsync(L.prm.hist, 0, L.clear_bytes, ctx->stream));
         const int sampled = wide && ctx->opt.minmax_single_read ? 1 : 0;  // (development variant: the ranges from a row-sample pass, round 3)
         const int single = sampled || predicted ? 1 : 0;
         const int grid = std::min(L.total_blocks, (REF ? 2 : 3) * 256), grid0 = std::min(L.total_blocks, 3 * 256);
@@ -1261,9 +1255,6 @@ int run_minmax(vszip_ctx *ctx, Launch &L, bool ref, bool no_thr, int batch, std:
 }  // namespace
 
 void vszip_planestats_release(vszip_ctx *ctx) {
-    if (ctx->minmax_pred) (void)hipFree(ctx->minmax_pred);
-    ctx->minmax_pred = nullptr;
-    ctx->minmax_pred_planes = 0;
     ctx->minmax_sig.clear();
     ctx->minmax_used.clear();
 }

@@ -2211,34 +2211,26 @@ VSZIP_EXPORT int vszip_ssimulacra2_src(vszip_ctx *ctx, const vszip_ssim_source *
         for (int c = 0; c < 3; ++c) nneed[s] += skip_of(c, s).all() ? 0 : 1;
     }
     const int tiles0 = ((w + TW - 1) / TW) * ((h + TH - 1) / TH);
-    // (every region starts on a multiple of 4 floats: the linear-RGB planes behind them are written and read with 16-byte accesses - ADVICE r5: 6 npx[3] + 6 npx[4]
-    // is 2 mod 4 for e.g. 1924 x 1080)
-    auto al4 = [](size_t n) { return (n + 3) & ~(size_t)3; };
-    const size_t f_x0 = al4(2 * nneed[0] * npx[0]), f_x1 = al4(2 * nneed[1] * npx[1]), f_r2 = al4(6 * npx[2]), f_xs = al4(6 * npx[2]), f_r3 = al4(6 * npx[3]), f_r4 = al4(6 * npx[4]);
-    const size_t f_rgb = (split || split_row) ? 6 * npx[0] : 0;  // the two frames' linear RGB between the pre-stage pass and the pyramid pass
-    const size_t f_pair = (f_x0 + f_x1 + f_r2 + f_xs + f_r3 + f_r4 + f_rgb + 63) & ~(size_t)63;
-    const size_t bytes_part = ((size_t)npairs * 18 * tiles0 * 6 * sizeof(double) + 255) & ~(size_t)255;
-    const size_t bytes_avg = ((size_t)npairs * 18 * 6 * sizeof(double) + 255) & ~(size_t)255;
-    const size_t bytes_tab = ((size_t)kScales * npairs * sizeof(PairPtrs) + 255) & ~(size_t)255;
-    const size_t bytes_pyr = ((size_t)npairs * sizeof(PyrPair) + 255) & ~(size_t)255;
-    const size_t need = bytes_part + bytes_avg + bytes_tab + bytes_pyr + (size_t)npairs * f_pair * sizeof(float) + 1024;
-    rc = vszip_ensure_scratch(ctx, need);
+    const scratch::SsimScratch lay = scratch::ssim_scratch(npx, nneed[0], nneed[1], (size_t)npairs, (size_t)tiles0, split || split_row, kScales, sizeof(PairPtrs), sizeof(PyrPair));
+    char *base;
+    rc = vszip_reserve_scratch(ctx, lay.all, &base);
     if (rc != VSZIP_OK) return rc;
-    rc = vszip_ensure_scalars(ctx, std::max(bytes_avg, bytes_tab + bytes_pyr));
+    rc = vszip_ensure_scalars(ctx, std::max(lay.avg_bytes, lay.tables.all.bytes()));
     if (rc != VSZIP_OK) return rc;
-    char *base = static_cast<char *>(ctx->scratch);
-    double *partial = reinterpret_cast<double *>(base);
-    PairPtrs *tab_dev = reinterpret_cast<PairPtrs *>(base + bytes_part + bytes_avg);
-    PyrPair *pyr_dev = reinterpret_cast<PyrPair *>(base + bytes_part + bytes_avg + bytes_tab);
-    float *fbase = reinterpret_cast<float *>(base + bytes_part + bytes_avg + bytes_tab + bytes_pyr);
+    double *partial = lay.partial.in(base);
+    char *tables_dev = lay.tables_at.in(base), *tables_host = static_cast<char *>(ctx->scalars_host);
+    PairPtrs *tab_dev = reinterpret_cast<PairPtrs *>(lay.tables.tab.in(tables_dev));
+    PyrPair *pyr_dev = reinterpret_cast<PyrPair *>(lay.tables.pyr.in(tables_dev));
 
     // plane pointers of every (scale, pair), staged in the pinned buffer (the final kernel overwrites it with the
     // averages, later in stream order)
-    PairPtrs *tab = static_cast<PairPtrs *>(ctx->scalars_host);
-    PyrPair *pyr = reinterpret_cast<PyrPair *>(static_cast<char *>(ctx->scalars_host) + bytes_tab);
-    std::memset(tab, 0, bytes_tab + bytes_pyr);
+    PairPtrs *tab = reinterpret_cast<PairPtrs *>(lay.tables.tab.in(tables_host));
+    PyrPair *pyr = reinterpret_cast<PyrPair *>(lay.tables.pyr.in(tables_host));
+    std::memset(tables_host, 0, lay.tables.all.bytes());
     for (int pair = 0; pair < npairs; ++pair) {
-        float *x0 = fbase + (size_t)pair * f_pair, *x1 = x0 + f_x0, *r2 = x1 + f_x1, *xs = r2 + f_r2, *r3 = xs + f_xs, *r4 = r3 + f_r3;
+        char *pbase = lay.pairs.in(base) + (size_t)pair * lay.pair.all.bytes();
+        float *x0 = lay.pair.x0.in(pbase), *x1 = lay.pair.x1.in(pbase), *r2 = lay.pair.r2.in(pbase), *xs = lay.pair.xs.in(pbase), *r3 = lay.pair.r3.in(pbase), *r4 = lay.pair.r4.in(pbase);
+        float *rgb = lay.pair.rgb.in(pbase);
         PyrPair &py = pyr[pair];
         for (int c = 0; c < nsp; ++c) {
             py.src1[c] = ref_planes[pair * nsp + c];
@@ -2274,12 +2266,12 @@ VSZIP_EXPORT int vszip_ssimulacra2_src(vszip_ctx *ctx, const vszip_ssim_source *
             py.r2a[c] = r2 + (size_t)c * npx[2];
             py.r2b[c] = r2 + (size_t)(3 + c) * npx[2];
             if (split || split_row) {
-                py.rgb1[c] = r4 + f_r4 + (size_t)c * npx[0];
-                py.rgb2[c] = r4 + f_r4 + (size_t)(3 + c) * npx[0];
+                py.rgb1[c] = rgb + (size_t)c * npx[0];
+                py.rgb2[c] = rgb + (size_t)(3 + c) * npx[0];
             }
         }
     }
-    VSZIP_HIP_CHECK(ctx, hipMemcpyAsync(tab_dev, tab, bytes_tab + bytes_pyr, hipMemcpyHostToDevice, ctx->stream));
+    VSZIP_HIP_CHECK(ctx, hipMemcpyAsync(tables_dev, tables_host, lay.tables.all.bytes(), hipMemcpyHostToDevice, ctx->stream));
 
     // ---- the launches, by piece (pairs [p0, p0 + cnt) on stream st) ----
     // scales 0 + 1 + the scale-2 RGB: one pass over the source
@@ -2477,7 +2469,8 @@ VSZIP_EXPORT int vszip_ssimulacra2_src(vszip_ctx *ctx, const vszip_ssim_source *
         FinalArgs fin;
         fin.partial = partial;
         // the averages go straight into the pinned host buffer (device-visible): no copy command at the end
-        VSZIP_HIP_CHECK(ctx, hipHostGetDevicePointer(reinterpret_cast<void **>(&fin.avg), ctx->scalars_host, 0));
+        rc = vszip_scalars_dev(ctx, &fin.avg);
+        if (rc != VSZIP_OK) return rc;
         fin.max_tiles = tiles0;
         for (int i = 0; i < 18; ++i) {
             fin.ntiles[i] = 0;

@@ -1060,7 +1060,8 @@ VSZIP_EXPORT int vszip_xpsnr_wsse_batch(vszip_ctx *ctx, int bytes_per_sample, in
     const size_t bps = (size_t)bytes_per_sample;
     XStripArgs sa;
     bool strips = (p.w % 2 == 0) && (p.h % 2 == 0) && !ctx->opt.xpsnr_blocks;
-    size_t tab_bytes = 0;
+    scratch::Layout lay;  // the frame table, where the kernel arguments cannot hold it
+    scratch::Region<XFrame> tab;
     if (strips) {
         sa.ncomp = num_comps;
         sa.luma_act = p.b >= 4;
@@ -1093,37 +1094,31 @@ VSZIP_EXPORT int vszip_xpsnr_wsse_batch(vszip_ctx *ctx, int bytes_per_sample, in
             g.segs = (std::min(g.by, g.h) + rs - 1) / rs;
             g.nstrips = g.nsx * g.segs * nby;
         }
-        if (nframes > kInlineFrames) tab_bytes = ((size_t)nframes * sizeof(XFrame) + 255) & ~(size_t)255;
+        tab = lay.take<XFrame>(nframes > kInlineFrames ? nframes : 0);
+        lay.align_to(256);
     }
 
     const size_t res_bytes = (size_t)nframes * p.total * sizeof(uint64_t);
     const size_t wsse_bytes = (size_t)nframes * 3 * sizeof(uint64_t);
     bool dev_weigh = p.n_luma <= (size_t)kWeighMaxBlocks && !ctx->opt.xpsnr_host_weigh;
     for (int c = 1; c < num_comps; ++c) dev_weigh = dev_weigh && (p.b < 4 || p.cn[c] <= p.n_luma);
-    if (tab_bytes) {
-        rc = vszip_ensure_scratch(ctx, tab_bytes);
+    char *base = nullptr;
+    if (lay.bytes()) {
+        rc = vszip_reserve_scratch(ctx, lay, &base);
         if (rc != VSZIP_OK) return rc;
     }
-    rc = vszip_ensure_scalars(ctx, std::max(dev_weigh ? wsse_bytes : res_bytes, tab_bytes));
+    rc = vszip_ensure_scalars(ctx, std::max(dev_weigh ? wsse_bytes : res_bytes, lay.bytes()));  // (the table is staged there)
     if (rc != VSZIP_OK) return rc;
     // The block sums live in a buffer of their own: the strip kernel accumulates into it with
     // atomics, the weighting kernel zeroes what it consumed, so a steady stream of calls never
     // pays for a memset.
-    if (res_bytes > ctx->xpsnr_sums_bytes) {
-        if (ctx->xpsnr_sums) {
-            VSZIP_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
-            (void)hipFree(ctx->xpsnr_sums);
-            ctx->xpsnr_sums = nullptr;
-            ctx->xpsnr_sums_bytes = 0;
-        }
-        const size_t want = std::max<size_t>(res_bytes * 2, 1 << 20);
-        if (vszip_hip_malloc(ctx, &ctx->xpsnr_sums, want) != hipSuccess) return vszip_set_error(ctx, VSZIP_ERR_NOMEM, "XPSNR : block sum buffer allocation failed");
-        ctx->xpsnr_sums_bytes = want;
-        ctx->xpsnr_clean = false;
-    }
-    uint64_t *dev = static_cast<uint64_t *>(ctx->xpsnr_sums);
+    bool grew;
+    rc = vszip_reserve(ctx, ctx->xpsnr_sums, res_bytes, std::max<size_t>(res_bytes * 2, 1 << 20), "XPSNR block sum buffer", &grew);
+    if (rc != VSZIP_OK) return rc;
+    if (grew) ctx->xpsnr_clean = false;
+    uint64_t *dev = static_cast<uint64_t *>(ctx->xpsnr_sums.ptr);
     if (!ctx->xpsnr_clean) {
-        VSZIP_HIP_CHECK(ctx, hipMemsetAsync(dev, 0, ctx->xpsnr_sums_bytes, ctx->stream));
+        VSZIP_HIP_CHECK(ctx, hipMemsetAsync(dev, 0, ctx->xpsnr_sums.bytes, ctx->stream));
         ctx->xpsnr_clean = true;
     }
 
@@ -1140,8 +1135,8 @@ VSZIP_EXPORT int vszip_xpsnr_wsse_batch(vszip_ctx *ctx, int bytes_per_sample, in
         if (nframes > kInlineFrames) {
             XFrame *host = static_cast<XFrame *>(ctx->scalars_host);  // pinned
             for (int f = 0; f < nframes; ++f) fill(host[f], f);
-            XFrame *tab_dev = static_cast<XFrame *>(ctx->scratch);
-            VSZIP_HIP_CHECK(ctx, hipMemcpyAsync(tab_dev, host, (size_t)nframes * sizeof(XFrame), hipMemcpyHostToDevice, ctx->stream));
+            XFrame *tab_dev = tab.in(base);
+            VSZIP_HIP_CHECK(ctx, hipMemcpyAsync(tab_dev, host, tab.bytes(), hipMemcpyHostToDevice, ctx->stream));
             sa.tab = tab_dev;
         } else {
             for (int f = 0; f < kInlineFrames; ++f) fill(sa.inl[f], std::min(f, nframes - 1));
@@ -1172,7 +1167,8 @@ VSZIP_EXPORT int vszip_xpsnr_wsse_batch(vszip_ctx *ctx, int bytes_per_sample, in
         WArgs wa;
         wa.sums = dev;
         // results go straight into the pinned host buffer (device-visible): no copy command
-        VSZIP_HIP_CHECK(ctx, hipHostGetDevicePointer(reinterpret_cast<void **>(&wa.wsse), ctx->scalars_host, 0));
+        rc = vszip_scalars_dev(ctx, &wa.wsse);
+        if (rc != VSZIP_OK) return rc;
         wa.total = (unsigned)p.total;
         wa.w = (int)p.w;
         wa.h = (int)p.h;
