@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define VSZIP_ABI_VERSION 4 /* additive since 4: vszip_clahe, vszip_comb_mask, vszip_comb_mask_mt, vszip_checkmate, vszip_mosquito_nr, vszip_deband, vszip_deband_tables, vszip_bilateral_dither, vszip_bilateral_dither_derive, vszip_bilateral_dither_points, vszip_compress, vszip_compress_tables, vszip_pack_rgb, vszip_color_map_lut, vszip_color_map, vszip_image_unpack; 4 (round 5): vszip_dev_alloc searches a bounded number of candidates and keeps nothing (below); vszip_dev_arena_info added; vszip_dev_trim, vszip_dev_placement_info and
+#define VSZIP_ABI_VERSION 4 /* additive since 4: vszip_clahe, vszip_comb_mask, vszip_comb_mask_mt, vszip_checkmate, vszip_mosquito_nr, vszip_deband, vszip_deband_tables, vszip_bilateral_dither, vszip_bilateral_dither_derive, vszip_bilateral_dither_points, vszip_compress, vszip_compress_tables, vszip_pack_rgb, vszip_color_map_lut, vszip_color_map, vszip_image_unpack, vszip_chain_ops; 4 (round 5): vszip_dev_alloc searches a bounded number of candidates and keeps nothing (below); vszip_dev_arena_info added; vszip_dev_trim, vszip_dev_placement_info and
                                vszip_dev_alloc_probed removed (nothing is searched for or parked any more); 3 (round 4): vszip_ctx_set_option / _get_option, vszip_dev_probe_region,
                                vszip_plane_average_async, vszip_plane_minmax_async added; 2 (round 3): vszip_ssim_source grew (YUV sources); entry points added since 1:
                                vszip_chain_run, vszip_ssimulacra2_src, vszip_to_rgbs_linear, vszip_probe_read_each, vszip_resample_table */
@@ -679,6 +679,92 @@ typedef struct vszip_chain_stage {
 } vszip_chain_stage;
 int vszip_chain_run(vszip_ctx *ctx, int dtype, const vszip_chain_stage *stages, int nstages,
                     const vszip_plane *planes, const int *plane_slot, int nplanes);
+
+/*
+ * vszip_chain_ops: resident chains over EVERY frame-in / frame-out filter of this header. What vszip_chain_run is for BoxBlur, Bilateral and
+ * Limiter, for the filters added since as well: Checkmate -> MosquitoNR -> Deband, Compress -> MosquitoNR, CLAHE -> Limiter, BoxBlur -> CombMask in
+ * one call, with the library owning every intermediate plane. vszip_chain_run is a translation of its stages into ops followed by this call: its
+ * stage struct is flat and per plane SLOT, while Deband's grain pointer, MosquitoNR's strengths and Compress's chroma flags are per table ENTRY and
+ * Checkmate and CombMask read neighbouring FRAMES, so the newer kinds live here.
+ *
+ * An op is (kind, process[3], params): process[k] as in vszip_chain_stage, and params points to ONE small struct of the kind, which holds exactly
+ * the arguments of that kind's entry point (the structs below, named after the VSZIP_STAGE_ number they belong to). All pointers are read before the
+ * call returns and may be reused at once, as with the entry points themselves. dtype is one sample type for the whole chain; bits_per_sample is what
+ * vszip_mosquito_nr and vszip_bilateral_dither take (8 for VSZIP_U8, 9..16 for VSZIP_U16, ignored for VSZIP_F32) and is not looked at when neither
+ * kind occurs.
+ *
+ * Not chain ops: the two-input joins (vszip_limit_filter, vszip_adaptive_binarize, vszip_bilateral and vszip_bilateral_dither with a `ref` clip) and
+ * the filters whose output has another format than their input (vszip_pack_rgb, vszip_color_map, vszip_image_unpack); a chain is one clip in, the
+ * same format out. The metric filters return scalars. A host runs those on the chain's dst planes, which are resident too.
+ *
+ * Rules.
+ * 1. Per-plane parameter arrays run beside the plane table. MosquitoNR's strength / restore / radius / chroma, Deband's per, BilateralDither's per
+ *    and Compress's chroma have nplanes entries each, entry i belonging to planes[i], exactly as the underlying entry points index them. The chain
+ *    compacts them to the entries the op processes; entries of slots the op skips are not read. A NULL where the entry point allows NULL
+ *    (MosquitoNR's and Compress's chroma) keeps its meaning. Bilateral's cfg and Limiter's lo / hi stay per plane slot, as in vszip_chain_stage.
+ * 2. Plane semantics are vszip_chain_run's. An op filters the entries whose slot it processes and passes the others through; the last op that writes
+ *    an entry writes the caller's dst; an entry no op writes is copied when dst != src. Every op reads and writes different memory: an entry
+ *    with two or more writers ping-pongs between the two halves of a region of its own in the context's chain buffer (dense rows at a 256-byte
+ *    pitch, grow-only), so the "dst must not overlap src" rules of Deband, MosquitoNR and the stencil filters hold by construction. What stays with
+ *    the caller: a dst plane overlaps no src plane of the table (dst == src of the same entry is fine where every op that writes dst allows it on
+ *    its own: a chain of one Limiter, say). planes[i].ref is not used: BilateralDither runs without `ref`, Bilateral with ref == src, and CombMask's
+ *    previous frame comes from the table (rule 3).
+ * 3. The table is a clip. frame[i] is the frame number of entry i; `frame` may be NULL when no op is temporal. The temporal ops are Checkmate, and
+ *    CombMask with mthresh > 0. With one present: within every plane slot the frame numbers form one contiguous range fmin..fmax, each
+ *    (slot, frame) pair occurs once, and all entries of a slot have the same w x h; anything else is VSZIP_ERR_ARG. A temporal op finds the
+ *    neighbours of entry i among the entries of the same slot and takes them where the PREVIOUS WRITING OP LEFT THEM (the caller's src if none
+ *    wrote yet): BoxBlur -> Checkmate is Checkmate on the blurred clip. Frame indices are clamped to the table's range exactly as the wrappers
+ *    clamp to the clip: Checkmate max(fmin, n - k) and min(n + k, fmax); CombMask max(fmin, n - 1), so frame fmin is its own `ref` and its motion
+ *    mask is all zero. A host passes whole clips or, for a window of one, the frames around it. No op reads what it writes: all entries of a slot
+ *    have been written equally often, an op reads only the halves earlier ops wrote (or src) and writes the other halves or the callers' dst
+ *    (csrc/chain_plan.hpp derives it; tests/chain_plan_check.cpp sweeps it).
+ * 4. Nothing is queued before the chain is known to be well formed. Checked for every op before the first launch, VSZIP_ERR_ARG with a
+ *    vszip_last_error text that names the op index ("chain: op 2 (Compress) does not take sample type 1"): the kind number; NULL params, and a NULL
+ *    pointer inside params where the entry point takes none (MosquitoNR's strength / restore / radius, Deband's and BilateralDither's per,
+ *    Compress's tables, Bilateral's cfg of a slot the op processes); the dtype a kind accepts (U8 only for CombMask, CombMaskMT, Checkmate and
+ *    Compress, whose entry points take no dtype and would read wider planes as bytes; U8 / U16 for CLAHE; U16 / F32 for Deband; U8 / U16 / F32 for
+ *    MosquitoNR and BilateralDither; U8 / U16 / F16 / F32 for BoxBlur and Bilateral; those and U32 for Limiter); bits_per_sample against dtype
+ *    where a kind uses it; the frame-table conditions of rule 3; and per plane a NULL src or dst, w or h below 1, a slot outside 0..2
+ *    ("chain: bad plane 3").
+ * 5. Value checks stay with the entry points: thresholds out of range, planes too small for a filter, a radius too large. Their status and their
+ *    wording come through unchanged. After such a failure the ops before the failing one have run and the contents of the dst planes are
+ *    unspecified; the next call on the context is correct all the same.
+ * Asynchronous on the context stream (growing the chain buffer drains it first).
+ */
+enum { VSZIP_STAGE_CLAHE = 3, VSZIP_STAGE_COMB_MASK = 4, VSZIP_STAGE_COMB_MASK_MT = 5, VSZIP_STAGE_CHECKMATE = 6, VSZIP_STAGE_MOSQUITO_NR = 7, VSZIP_STAGE_DEBAND = 8,
+       VSZIP_STAGE_BILATERAL_DITHER = 9, VSZIP_STAGE_COMPRESS = 10 };
+typedef struct vszip_chain_op {
+    int32_t kind;       /* VSZIP_STAGE_* */
+    int32_t process[3]; /* per plane slot */
+    const void *params; /* the struct of `kind` below */
+} vszip_chain_op;
+typedef struct vszip_chain_boxblur { int32_t hradius, hpasses, vradius, vpasses; } vszip_chain_boxblur;
+typedef struct vszip_chain_bilateral {
+    const struct vszip_bilateral_cfg *cfg[3]; /* per plane slot, LUTs resident */
+    float peak;
+} vszip_chain_bilateral;
+typedef struct vszip_chain_limiter { double lo[3], hi[3]; /* per plane slot */ } vszip_chain_limiter;
+typedef struct vszip_chain_clahe { uint32_t limit; int32_t tiles_x, tiles_y; } vszip_chain_clahe;
+typedef struct vszip_chain_comb_mask { int32_t cthresh, mthresh, expand, metric; } vszip_chain_comb_mask;
+typedef struct vszip_chain_comb_mask_mt { int32_t thy1, thy2; } vszip_chain_comb_mask_mt;
+typedef struct vszip_chain_checkmate { int32_t thr, tmax, tthr2; } vszip_chain_checkmate;
+typedef struct vszip_chain_mosquito_nr {
+    const int32_t *strength, *restore, *radius; /* nplanes entries each */
+    const uint8_t *chroma;                      /* nplanes entries, or NULL */
+} vszip_chain_mosquito_nr;
+typedef struct vszip_chain_deband {
+    const vszip_deband_plane *per; /* nplanes entries */
+    int32_t sample_mode, blur_first;
+    float angle_boost, max_angle;
+    int32_t max_offset;
+} vszip_chain_deband;
+typedef struct vszip_chain_bilateral_dither { const vszip_bilateral_dither_plane *per; /* nplanes entries */ } vszip_chain_bilateral_dither;
+typedef struct vszip_chain_compress {
+    const struct vszip_compress_tables *tables;
+    const uint8_t *chroma; /* nplanes entries, or NULL */
+} vszip_chain_compress;
+int vszip_chain_ops(vszip_ctx *ctx, int dtype, int bits_per_sample, const vszip_chain_op *ops, int nops,
+                    const vszip_plane *planes, const int *plane_slot, const int *frame, int nplanes);
 
 /*
  * SSIMULACRA2 — replaces filter_ssim.process (src/filters/ssimulacra2.zig:46) called from

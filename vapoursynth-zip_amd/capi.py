@@ -121,6 +121,76 @@ class ChainStage(C.Structure):
 
 
 STAGE_BOXBLUR, STAGE_BILATERAL, STAGE_LIMITER = 0, 1, 2
+(STAGE_CLAHE, STAGE_COMB_MASK, STAGE_COMB_MASK_MT, STAGE_CHECKMATE, STAGE_MOSQUITO_NR, STAGE_DEBAND, STAGE_BILATERAL_DITHER,
+ STAGE_COMPRESS) = range(3, 11)
+
+
+class ChainOp(C.Structure):
+    """vszip_chain_op"""
+    _fields_ = [("kind", C.c_int32), ("process", C.c_int32 * 3), ("params", C.c_void_p)]
+
+
+class ChainBoxBlur(C.Structure):
+    """vszip_chain_boxblur"""
+    _fields_ = [("hradius", C.c_int32), ("hpasses", C.c_int32), ("vradius", C.c_int32), ("vpasses", C.c_int32)]
+
+
+class ChainBilateral(C.Structure):
+    """vszip_chain_bilateral"""
+    _fields_ = [("cfg", C.POINTER(BilateralCfg) * 3), ("peak", C.c_float)]
+
+
+class ChainLimiter(C.Structure):
+    """vszip_chain_limiter"""
+    _fields_ = [("lo", C.c_double * 3), ("hi", C.c_double * 3)]
+
+
+class ChainClahe(C.Structure):
+    """vszip_chain_clahe"""
+    _fields_ = [("limit", C.c_uint32), ("tiles_x", C.c_int32), ("tiles_y", C.c_int32)]
+
+
+class ChainCombMask(C.Structure):
+    """vszip_chain_comb_mask"""
+    _fields_ = [("cthresh", C.c_int32), ("mthresh", C.c_int32), ("expand", C.c_int32), ("metric", C.c_int32)]
+
+
+class ChainCombMaskMT(C.Structure):
+    """vszip_chain_comb_mask_mt"""
+    _fields_ = [("thy1", C.c_int32), ("thy2", C.c_int32)]
+
+
+class ChainCheckmate(C.Structure):
+    """vszip_chain_checkmate"""
+    _fields_ = [("thr", C.c_int32), ("tmax", C.c_int32), ("tthr2", C.c_int32)]
+
+
+class ChainMosquitoNR(C.Structure):
+    """vszip_chain_mosquito_nr"""
+    _fields_ = [("strength", C.POINTER(C.c_int32)), ("restore", C.POINTER(C.c_int32)), ("radius", C.POINTER(C.c_int32)), ("chroma", C.POINTER(C.c_uint8))]
+
+
+class ChainDeband(C.Structure):
+    """vszip_chain_deband"""
+    _fields_ = [("per", C.POINTER(DebandPlane)), ("sample_mode", C.c_int32), ("blur_first", C.c_int32), ("angle_boost", C.c_float), ("max_angle", C.c_float),
+                ("max_offset", C.c_int32)]
+
+
+class ChainBilateralDither(C.Structure):
+    """vszip_chain_bilateral_dither"""
+    _fields_ = [("per", C.POINTER(BilateralDitherPlane))]
+
+
+class ChainCompress(C.Structure):
+    """vszip_chain_compress"""
+    _fields_ = [("tables", C.POINTER(CompressTables)), ("chroma", C.POINTER(C.c_uint8))]
+
+
+# C name -> ctypes class of every struct of vszip_chain_ops (tests/test_chain_plan_host.py compares sizes and offsets with the compiler's)
+CHAIN_STRUCTS = {"vszip_chain_op": ChainOp, "vszip_chain_boxblur": ChainBoxBlur, "vszip_chain_bilateral": ChainBilateral, "vszip_chain_limiter": ChainLimiter,
+                 "vszip_chain_clahe": ChainClahe, "vszip_chain_comb_mask": ChainCombMask, "vszip_chain_comb_mask_mt": ChainCombMaskMT,
+                 "vszip_chain_checkmate": ChainCheckmate, "vszip_chain_mosquito_nr": ChainMosquitoNR, "vszip_chain_deband": ChainDeband,
+                 "vszip_chain_bilateral_dither": ChainBilateralDither, "vszip_chain_compress": ChainCompress}
 
 
 class SsimSource(C.Structure):
@@ -174,6 +244,7 @@ SYMBOLS = {
     "vszip_bilateral": (_i, [_vp, _i, _PP, C.POINTER(C.POINTER(BilateralCfg)), _i, C.c_float]),
     "vszip_ssimulacra2": (_i, [_vp, C.POINTER(_vp), C.POINTER(_vp), _pd, _i, _i, _i, C.POINTER(C.c_double)]),
     "vszip_chain_run": (_i, [_vp, _i, C.POINTER(ChainStage), _i, _PP, C.POINTER(C.c_int), _i]),
+    "vszip_chain_ops": (_i, [_vp, _i, _i, C.POINTER(ChainOp), _i, _PP, C.POINTER(C.c_int), C.POINTER(C.c_int), _i]),
     "vszip_resample_table": (_i, [_i, _i, C.c_double, C.POINTER(C.c_int32), C.POINTER(C.c_float)]),
     "vszip_ssimulacra2_src": (_i, [_vp, C.POINTER(SsimSource), C.POINTER(_vp), C.POINTER(_vp), _pd, _i, _i, _i, C.POINTER(C.c_double)]),
     "vszip_to_rgbs_linear": (_i, [_vp, C.POINTER(SsimSource), C.POINTER(_vp), _pd, C.POINTER(_vp), _pd, _i, _i]),
@@ -1006,6 +1077,105 @@ class Device:
         n = len(srcs)
         slots = (C.c_int * n)(*plane_slot)
         self.check(self.lib.vszip_chain_run(self.ctx, _NP2DT[srcs[0].dtype], arr, len(stages), self.plane_table(srcs, dsts), slots, n))
+
+    def chain_ops(self, ops, srcs, dsts, plane_slot, frames=None, bits=None):
+        """vszip_chain_ops: a chain over every frame-in / frame-out filter on resident planes in one call, intermediates owned by the context.
+        ops: list of dicts, one key per kind and an optional "planes": (bool, bool, bool) each -
+          {"boxblur": (hr, hp, vr, vp)} | {"bilateral": cfg, "peak": p} | {"limiter": (lo3, hi3)}                       as chain_run
+          {"clahe": (limit, tiles)} | {"comb_mask": dict(cthresh, mthresh, expand, metric)} | {"comb_mask_mt": (thY1, thY2)}
+          {"checkmate": dict(thr, tmax, tthr2)} | {"compress": tables, "chroma": per entry | scalar | None}
+          {"mosquito_nr": dict(strength, restore, radius, chroma)}      scalars, or one value per table ENTRY (len(srcs) values)
+          {"deband": entries, sample_mode=, blur_first=, angle_boost=, max_angle=, max_offset=}   entries: one deband_entry per table entry (None
+                                                                                                  where the op skips the entry)
+          {"bilateral_dither": entries}                                 one bilateral_dither_entry per table entry (None where skipped)
+        plane_slot[i] in 0..2; frames[i]: the frame number of entry i (needed by checkmate and by comb_mask with mthresh > 0: the table is a
+        clip, and the neighbouring frames are the table's other entries of the slot, as the op before left them). bits: bits per sample for
+        mosquito_nr / bilateral_dither (default: the sample width)."""
+        args, _keep = self._chain_ops_args(ops, srcs, dsts, plane_slot, frames, bits)
+        self.check(self.lib.vszip_chain_ops(self.ctx, *args))
+
+    def _chain_ops_args(self, ops, srcs, dsts, plane_slot, frames=None, bits=None):
+        """the argument blocks of vszip_chain_ops for chain_ops() / prepared_chain_ops(), and what must stay alive while they are used"""
+        n = len(srcs)
+        keep = []  # the params blocks: alive until the call returns
+
+        def hold(x):
+            keep.append(x)
+            return x
+
+        def per_entry(v, ctype, default=None):
+            if v is None:
+                v = default
+            if v is None:
+                return None
+            vals = [v] * n if isinstance(v, (bool, int, np.integer)) else list(v)
+            if len(vals) != n:
+                raise ValueError("chain_ops: a per-plane parameter is a scalar or has one value per table entry")
+            return hold((ctype * n)(*[int(x) for x in vals]))
+
+        def structs(entries, cls):
+            if len(entries) != n:
+                raise ValueError("chain_ops: one parameter entry (or None) per table entry")
+            return hold((cls * n)(*[e if e is not None else cls() for e in entries]))
+
+        arr = (ChainOp * len(ops))()
+        for op, d in zip(arr, ops):
+            pr = d.get("planes", (True, True, True))
+            for k in range(3):
+                op.process[k] = int(bool(pr[k]))
+            if "boxblur" in d:
+                op.kind, prm = STAGE_BOXBLUR, ChainBoxBlur(*[int(v) for v in d["boxblur"]])
+            elif "bilateral" in d:
+                op.kind, prm = STAGE_BILATERAL, ChainBilateral()
+                for k in range(3):
+                    prm.cfg[k] = C.pointer(d["bilateral"][k])
+                    op.process[k] = int(bool(pr[k]) and bool(d["bilateral"][k].process))
+                prm.peak = d["peak"]
+            elif "limiter" in d:
+                op.kind, prm = STAGE_LIMITER, ChainLimiter()
+                for k in range(3):
+                    prm.lo[k], prm.hi[k] = d["limiter"][0][k], d["limiter"][1][k]
+            elif "clahe" in d:
+                limit, tiles = d["clahe"]
+                op.kind, prm = STAGE_CLAHE, ChainClahe(int(limit), *self.clahe_tiles(tiles))
+            elif "comb_mask" in d:
+                a = dict(cthresh=6, mthresh=9, expand=True, metric=0)
+                a.update(d["comb_mask"])
+                op.kind, prm = STAGE_COMB_MASK, ChainCombMask(int(a["cthresh"]), int(a["mthresh"]), int(bool(a["expand"])), int(a["metric"]))
+            elif "comb_mask_mt" in d:
+                op.kind, prm = STAGE_COMB_MASK_MT, ChainCombMaskMT(*[int(v) for v in d["comb_mask_mt"]])
+            elif "checkmate" in d:
+                a = dict(thr=12, tmax=12, tthr2=0)
+                a.update(d["checkmate"])
+                op.kind, prm = STAGE_CHECKMATE, ChainCheckmate(int(a["thr"]), int(a["tmax"]), int(a["tthr2"]))
+            elif "mosquito_nr" in d:
+                a = d["mosquito_nr"]
+                op.kind, prm = STAGE_MOSQUITO_NR, ChainMosquitoNR(per_entry(a.get("strength"), C.c_int32, 16), per_entry(a.get("restore"), C.c_int32, 128),
+                                                                  per_entry(a.get("radius"), C.c_int32, 2), per_entry(a.get("chroma"), C.c_uint8))
+            elif "deband" in d:
+                op.kind, prm = STAGE_DEBAND, ChainDeband(structs(d["deband"], DebandPlane), int(d.get("sample_mode", 2)), int(bool(d.get("blur_first", True))),
+                                                         float(d.get("angle_boost", 1.5)), float(d.get("max_angle", 0.15)), int(d.get("max_offset", 128)))
+            elif "bilateral_dither" in d:
+                op.kind, prm = STAGE_BILATERAL_DITHER, ChainBilateralDither(structs(d["bilateral_dither"], BilateralDitherPlane))
+            elif "compress" in d:
+                op.kind, prm = STAGE_COMPRESS, ChainCompress(C.pointer(d["compress"]) if d["compress"] is not None else None, per_entry(d.get("chroma"), C.c_uint8))
+            elif "raw" in d:  # (kind, address of a params block or None): what a C host could pass (tests of the refusals)
+                op.kind, prm = int(d["raw"][0]), None
+                op.params = d["raw"][1]
+            else:
+                raise ValueError(f"chain_ops: no known kind in {sorted(d)}")
+            if prm is not None:
+                op.params = C.addressof(hold(prm))
+        dt = srcs[0].dtype
+        slots = (C.c_int * n)(*plane_slot)
+        fr = (C.c_int * n)(*[int(f) for f in frames]) if frames is not None else None
+        b = int(bits) if bits is not None else 8 * dt.itemsize
+        return (_NP2DT[dt], b, arr, len(ops), self.plane_table(srcs, dsts), slots, fr, n), keep
+
+    def prepared_chain_ops(self, ops, srcs, dsts, plane_slot, frames=None, bits=None):
+        """-> a callable queueing vszip_chain_ops on argument blocks built once."""
+        fn, ctx, check, (args, keep) = self.lib.vszip_chain_ops, self.ctx, self.check, self._chain_ops_args(ops, srcs, dsts, plane_slot, frames, bits)
+        return lambda _keep=keep: check(fn(ctx, *args))
 
     @staticmethod
     def ssim_source(family: str, dtype, bits=None, linearize=True, limited=None, ssw=0, ssh=0, matrix=1, chroma_loc=0) -> SsimSource:
