@@ -181,7 +181,10 @@ int vszip_probe_read_each(vszip_ctx *ctx, double *total_ms, int *launches, float
  *    and up to four planes out: its reads stay inside the w x pixel-bytes of each of the h source rows (the source's pitch is in bytes
  *    and its padding is never read), only [0, w) x h of each output plane is written, and the outputs overlap neither each other nor
  *    src. The source needs no alignment at all; frames whose output bases and pitches (in bytes) are multiples of 16 take the fast
- *    path, every other frame a slower one with the same bits.
+ *    path, every other frame a slower one with the same bits. vszip_depth converts one plane into one plane of another sample width:
+ *    its reads stay inside [0, w) x h of src, only [0, w) x h of dst is written, dst overlaps no src, and bases and pitches (in
+ *    bytes) that are not multiples of 16 take per-sample accesses with the same bits. vszip_deband_lowbit is vszip_deband's clauses
+ *    on planes of the lower depth.
  */
 typedef struct vszip_plane {
     const void *src; /* input plane */
@@ -354,8 +357,8 @@ int vszip_mosquito_nr(vszip_ctx *ctx, int dtype, int bits_per_sample, const vszi
  * random_algo_ref / _grain [0..2] ('Deband: parameter "range=256" out of range [0..255].'). The checks of thr, thr1, thr2 and
  * grain are on the wrapper's 8-bit scale and stay with the host; angle_boost and max_angle are checked by vszip_deband.
  *
- * vszip_deband. dtype VSZIP_U16 (samples on the 16-bit scale: the reference always works at 16 bits; the conversion of
- * clips under 16 bits and the dither back are the host's resizer) or VSZIP_F32. planes[i].src / dst as everywhere (`ref` is
+ * vszip_deband. dtype VSZIP_U16 (samples on the 16-bit scale: the reference always works at 16 bits; clips under 16 bits go
+ * through vszip_deband_lowbit below, which converts up, runs these kernels and dithers back on the device) or VSZIP_F32. planes[i].src / dst as everywhere (`ref` is
  * not used); per[i] sits beside planes[i] as vszip_temporal_nbrs does:
  *   offsets, offsets_pitch  DEVICE pointer to the plane's table (luma or chroma) and its row pitch in pairs;
  *   ssw, ssh                the shifts to apply to the table's values (0 for luma);
@@ -405,6 +408,47 @@ int vszip_deband_tables(const vszip_deband_cfg *cfg, vszip_deband_sizes *sizes, 
                         void *grain_c, uint32_t *grain_offsets, int32_t *max_offset, char *err, size_t err_cap);
 int vszip_deband(vszip_ctx *ctx, int dtype, const vszip_plane *planes, const vszip_deband_plane *per, int nplanes,
                  int sample_mode, int blur_first, float angle_boost, float max_angle, int max_offset);
+
+/*
+ * Depth — integer depth conversion as zimg's resize.Point does it with dither_type none and error_diffusion: what hz.bitDepth
+ * (src/helper.zig:470-494) asks the host's resizer for around Deband (src/vapoursynth/deband.zig:462-464, :494-497) and XPSNR. One
+ * vszip_depth_plane per conversion: src a plane of bits_in, dst a plane of bits_out, 8 bits stored as uint8_t and 9..16 as uint16_t,
+ * strides in elements of the plane's own sample type. Any number of planes of any mix of sizes in one call, w, h >= 1.
+ *   scale   limited range: 2^(bits_out - bits_in). Full range, chroma 0 (RGB, gray, full-range luma): (2^bits_out - 1) / (2^bits_in - 1),
+ *           divided in double and rounded to float. Full range with chroma set has a non-zero offset whose rounding no recorded data
+ *           pins: VSZIP_ERR_UNSUPPORTED.
+ *   dither 0 (none)             q = rint(min(max((float)src * scale, 0), 2^bits_out - 1)), half to even; one streaming pass.
+ *   dither 1 (error diffusion)  Floyd-Steinberg in f32, rows top to bottom, samples left to right, every product and sum rounded on its
+ *           own: err = 0 + left * 7/16; err += top[x + 1] * 3/16; err += top[x] * 5/16; err += top[x - 1] * 1/16;
+ *           v = min(max(src * scale + err, 0), peak); q = rint(v); the sample's error is v - q; errors outside the plane are 0.
+ *           Bit-exact with the reference's 8-bit Deband goldens (limited range 16 -> 8); the full-range case rests on this statement alone
+ *           (DESIGN.md 3.18). One workgroup walks one plane as a skewed wavefront (csrc/depth_plan.hpp); a plane of more rows than a
+ *           workgroup holds and more than 4096 columns keeps one row of errors in the context's scratch (grow-only).
+ * Asynchronous on the context stream. "Plane memory": reads stay inside [0, w) x h of src; only [0, w) x h of dst is written; dst overlaps
+ * no src. vszip_depth_check (device-free) is the argument check vszip_depth makes first, with the text in `err` (may be NULL):
+ * VSZIP_ERR_ARG for bits_in or bits_out outside 8..16 ("Depth: bits_in 7 is outside 8..16"), a dither other than 0 or 1, no planes,
+ * and, naming the plane ("Depth: plane 1: src and dst must not be NULL"), a NULL plane, w or h below 1, a pitch below w;
+ * VSZIP_ERR_UNSUPPORTED for full-range chroma.
+ *
+ * vszip_deband_lowbit — vszip_deband on planes of `bits` = 8..15 (uint8_t for 8), as the wrapper runs Deband on clips under 16 bits:
+ * per plane group, up to 16 bits with dither none, the kernels of vszip_deband, down to `bits` with error diffusion, on two 16-bit
+ * intermediates per plane in the context's scratch (beside sample mode 7's angle planes; at most VSZIP_DEBAND_LOWBIT_SCRATCH_MIB of
+ * intermediates per plane group, a plane is never split). per[i] stays on the 16-bit scale, exactly as vszip_deband takes it.
+ * full_range 1 declares every plane non-chroma (RGB, gray); a full-range YUV clip's chroma is not served. Errors: vszip_deband's and
+ * vszip_depth's, and VSZIP_ERR_ARG for bits outside 8..15.
+ */
+typedef struct vszip_depth_plane {
+    const void *src;
+    ptrdiff_t src_stride;
+    void *dst;
+    ptrdiff_t dst_stride;
+    int32_t w, h;
+    int32_t chroma; /* the plane is U or V of a YUV clip */
+} vszip_depth_plane;
+int vszip_depth_check(int bits_in, int bits_out, int dither, int full_range, const vszip_depth_plane *planes, int nplanes, char *err, size_t err_cap);
+int vszip_depth(vszip_ctx *ctx, const vszip_depth_plane *planes, int nplanes, int bits_in, int bits_out, int dither, int full_range);
+int vszip_deband_lowbit(vszip_ctx *ctx, int bits, int full_range, const vszip_plane *planes, const vszip_deband_plane *per, int nplanes,
+                        int sample_mode, int blur_first, float angle_boost, float max_angle, int max_offset);
 
 /*
  * BilateralDither — the port of dither's Dither_bilateral16: replaces processPlane of src/filters/bilateral_dither.zig:34-213

@@ -91,6 +91,16 @@ class PackRGBFrame(C.Structure):
                 ("dst", C.c_void_p), ("dst_stride", C.c_ssize_t), ("w", C.c_int32), ("h", C.c_int32)]
 
 
+class DepthPlane(C.Structure):
+    """vszip_depth_plane"""
+    _fields_ = [("src", C.c_void_p), ("src_stride", C.c_ssize_t), ("dst", C.c_void_p), ("dst_stride", C.c_ssize_t), ("w", C.c_int32), ("h", C.c_int32),
+                ("chroma", C.c_int32)]
+
+
+DEPTH_STRUCTS = {"vszip_depth_plane": DepthPlane}
+DITHER_NONE, DITHER_ERROR_DIFFUSION = 0, 1
+
+
 class ColorMapFrame(C.Structure):
     """vszip_color_map_frame"""
     _fields_ = [("src", C.c_void_p), ("src_stride", C.c_ssize_t), ("r", C.c_void_p), ("g", C.c_void_p), ("b", C.c_void_p),
@@ -266,6 +276,9 @@ SYMBOLS = {
     "vszip_mosquito_nr": (_i, [_vp, _i, _i, _PP, _i, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_uint8)]),
     "vszip_deband_tables": (_i, [C.POINTER(DebandCfg), C.POINTER(DebandSizes), _vp, _vp, _vp, _vp, _vp, C.POINTER(C.c_int32), C.c_char_p, _sz]),
     "vszip_deband": (_i, [_vp, _i, _PP, C.POINTER(DebandPlane), _i, _i, _i, C.c_float, C.c_float, _i]),
+    "vszip_depth_check": (_i, [_i, _i, _i, _i, C.POINTER(DepthPlane), _i, C.c_char_p, _sz]),
+    "vszip_depth": (_i, [_vp, C.POINTER(DepthPlane), _i, _i, _i, _i, _i]),
+    "vszip_deband_lowbit": (_i, [_vp, _i, _i, _PP, C.POINTER(DebandPlane), _i, _i, _i, C.c_float, C.c_float, _i]),
     "vszip_bilateral_dither_derive": (_i, [_i, _i, _i, C.c_float, C.c_float, C.c_float, C.c_float, C.POINTER(BilateralDitherCfg), C.c_char_p, _sz]),
     "vszip_bilateral_dither_points": (_i, [_i, C.c_float, _vp, _sz, C.POINTER(C.c_int32)]),
     "vszip_bilateral_dither": (_i, [_vp, _i, _i, _PP, C.POINTER(BilateralDitherPlane), _i]),
@@ -292,6 +305,17 @@ def resample_table(src_dim: int, dst_dim: int, shift: float = 0.0):
     if rc != 0:
         raise ValueError(f"vszip_resample_table({src_dim}, {dst_dim}, {shift}) -> {rc}")
     return left, coef
+
+
+def depth_check(bits_in, bits_out, dither, full_range, planes) -> None:
+    """vszip_depth_check (device-free): the argument checks of vszip_depth; planes: (src, src_stride, dst, dst_stride, w, h, chroma) tuples of plain
+    integers (pointers are only compared with NULL). VszipError with the library's code and text."""
+    n = len(planes)
+    arr = (DepthPlane * max(n, 1))(*[DepthPlane(*p) for p in planes])
+    err = C.create_string_buffer(256)
+    rc = load().vszip_depth_check(int(bits_in), int(bits_out), int(dither), int(full_range), arr if n else None, n, err, len(err))
+    if rc != 0:
+        raise VszipError(rc, err.value.decode())
 
 
 def deband_tables(width, height, ssw=0, ssh=0, num_frames=1, range=15, sample_mode=2, seed=0, random_algo_ref=1, random_algo_grain=1, random_param_ref=1.0,
@@ -917,6 +941,50 @@ class Device:
     def prepared_deband(self, srcs, dsts, entries, sample_mode=2, blur_first=True, angle_boost=1.5, max_angle=0.15, max_offset=128):
         """-> a callable queueing vszip_deband on argument blocks built once."""
         fn, ctx, check, args = self.lib.vszip_deband, self.ctx, self.check, self._deband_args(srcs, dsts, entries, sample_mode, blur_first, angle_boost, max_angle, max_offset)
+        return lambda: check(fn(ctx, *args))
+
+    def deband_lowbit(self, srcs, dsts, entries, bits, full_range=False, sample_mode=2, blur_first=True, angle_boost=1.5, max_angle=0.15, max_offset=128):
+        """vszip.Deband on planes of `bits` = 8..15 (u8 for 8, else u16), resident: up to 16 bits, vszip_deband's kernels, error-diffusion dither
+        back. entries as for deband(), on the 16-bit scale. full_range declares every plane non-chroma."""
+        self.check(self.lib.vszip_deband_lowbit(self.ctx, *self._deband_lowbit_args(srcs, dsts, entries, bits, full_range, sample_mode, blur_first, angle_boost, max_angle,
+                                                                                     max_offset)))
+
+    def prepared_deband_lowbit(self, srcs, dsts, entries, bits, full_range=False, sample_mode=2, blur_first=True, angle_boost=1.5, max_angle=0.15, max_offset=128):
+        """-> a callable queueing vszip_deband_lowbit on argument blocks built once."""
+        fn, ctx, check = self.lib.vszip_deband_lowbit, self.ctx, self.check
+        args = self._deband_lowbit_args(srcs, dsts, entries, bits, full_range, sample_mode, blur_first, angle_boost, max_angle, max_offset)
+        return lambda: check(fn(ctx, *args))
+
+    def _deband_lowbit_args(self, srcs, dsts, entries, bits, full_range, sample_mode, blur_first, angle_boost, max_angle, max_offset):
+        want = np.uint8 if int(bits) == 8 else np.uint16
+        if any(p.dtype != want for p in (*srcs, *dsts)):
+            raise ValueError(f"deband_lowbit: bits={bits} takes {np.dtype(want).name} planes")
+        return (int(bits), int(bool(full_range))) + self._deband_args(srcs, dsts, entries, sample_mode, blur_first, angle_boost, max_angle, max_offset)[1:]
+
+    def _depth_args(self, srcs, dsts, bits_in, bits_out, dither, full_range, chroma):
+        n = len(srcs)
+        ch = [int(bool(chroma))] * n if chroma is None or np.isscalar(chroma) else [int(bool(c)) for c in chroma]
+        if len(dsts) != n or len(ch) != n:
+            raise ValueError("depth: one destination (and one chroma flag) per plane")
+        for name, ps, bits in (("source", srcs, bits_in), ("destination", dsts, bits_out)):
+            want = np.uint8 if int(bits) == 8 else np.uint16
+            if 8 <= int(bits) <= 16 and any(p.dtype != want for p in ps):
+                raise ValueError(f"depth: {bits}-bit {name} planes are {np.dtype(want).name}")
+        if any((s.w, s.h) != (d.w, d.h) for s, d in zip(srcs, dsts)):
+            raise ValueError("depth: a destination has its source's size")
+        arr = (DepthPlane * n)()
+        for i in range(n):
+            arr[i] = DepthPlane(srcs[i].ptr, srcs[i].stride, dsts[i].ptr, dsts[i].stride, srcs[i].w, srcs[i].h, ch[i])
+        return (arr, n, int(bits_in), int(bits_out), int(dither), int(bool(full_range)))
+
+    def depth(self, srcs, dsts, bits_in, bits_out, dither=DITHER_NONE, full_range=False, chroma=None):
+        """vszip_depth on every plane: srcs at bits_in, dsts at bits_out (u8 for 8 bits, u16 for 9..16), any mix of sizes; dither DITHER_NONE or
+        DITHER_ERROR_DIFFUSION; chroma a scalar or one flag per plane (full-range chroma is VSZIP_ERR_UNSUPPORTED). dsts overlap no source."""
+        self.check(self.lib.vszip_depth(self.ctx, *self._depth_args(srcs, dsts, bits_in, bits_out, dither, full_range, chroma)))
+
+    def prepared_depth(self, srcs, dsts, bits_in, bits_out, dither=DITHER_NONE, full_range=False, chroma=None):
+        """-> a callable queueing vszip_depth on argument blocks built once."""
+        fn, ctx, check, args = self.lib.vszip_depth, self.ctx, self.check, self._depth_args(srcs, dsts, bits_in, bits_out, dither, full_range, chroma)
         return lambda: check(fn(ctx, *args))
 
     def upload_bilateral_dither_points(self, pts: np.ndarray) -> DevPlane:

@@ -104,6 +104,7 @@ const OptionRange kRanges[] = {
     {"VSZIP_CLAHE_SCRATCH_MIB", 1, 1 << 20},
     {"VSZIP_DEBAND_SCRATCH_MIB", 1, 1 << 20}, {"VSZIP_DEBAND_PATH", 0, 2},
     {"VSZIP_BILATERAL_DITHER_PATH", 0, 2},
+    {"VSZIP_DEBAND_LOWBIT_SCRATCH_MIB", 1, 1 << 20}, {"VSZIP_DEPTH_WAVES", 0, 16},
 };
 bool option_in_range(const char *env, int v) {
     for (const OptionRange &r : kRanges)

@@ -23,6 +23,7 @@
 #include <cstdlib>
 
 #include "deband_body.hpp"
+#include "depth.hpp"
 #include "plane_table.hpp"
 
 namespace {
@@ -102,14 +103,16 @@ int range_error(vszip_ctx *ctx, const char *key, double v, int lo, int hi) {
     return vszip_set_error(ctx, VSZIP_ERR_ARG, "Deband: parameter \"%s=%s\" out of range [%d..%d].", key, num, lo, hi);
 }
 
-}  // namespace
+// vszip_deband_lowbit: the planes are at `bits` and pass through two 16-bit intermediates of the group's scratch
+struct LowBit {
+    int bits, full_range;
+};
 
-VSZIP_EXPORT int vszip_deband(vszip_ctx *ctx, int dtype, const vszip_plane *planes, const vszip_deband_plane *per, int nplanes, int sample_mode, int blur_first,
-                              float angle_boost, float max_angle, int max_offset) {
-    if (!ctx) return VSZIP_ERR_ARG;
+int deband_run(vszip_ctx *ctx, int dtype, const vszip_plane *planes, const vszip_deband_plane *per, int nplanes, int sample_mode, int blur_first, float angle_boost,
+               float max_angle, int max_offset, const LowBit *low) {
     if (!planes || !per || nplanes <= 0) return vszip_set_error(ctx, VSZIP_ERR_ARG, "Deband: no planes");
     if (dtype != VSZIP_U16 && dtype != VSZIP_F32)
-        return vszip_set_error(ctx, VSZIP_ERR_ARG, "Deband: 16-bit integer or 32-bit float planes only (clips under 16 bits are converted by the host).");
+        return vszip_set_error(ctx, VSZIP_ERR_ARG, "Deband: 16-bit integer or 32-bit float planes only (clips under 16 bits go through vszip_deband_lowbit).");
     if (sample_mode < 1 || sample_mode > 7) return range_error(ctx, "sample_mode", sample_mode, 1, 7);
     if (!(angle_boost >= 0.0f && angle_boost <= 65535.0f)) return range_error(ctx, "angle_boost", angle_boost, 0, 65535);
     if (!(max_angle >= 0.0f && max_angle <= 1.0f)) return range_error(ctx, "max_angle", max_angle, 0, 1);
@@ -121,6 +124,28 @@ VSZIP_EXPORT int vszip_deband(vszip_ctx *ctx, int dtype, const vszip_plane *plan
         if (d.ssw < 0 || d.ssw > 4 || d.ssh < 0 || d.ssh > 4) return vszip_set_error(ctx, VSZIP_ERR_ARG, "Deband: plane %d: subsampling %d/%d is outside 0..4", i, d.ssw, d.ssh);
         if (d.offsets_pitch < s.w || (d.grain && d.grain_pitch < s.w)) return vszip_set_error(ctx, VSZIP_ERR_ARG, "Deband: plane %d: a table pitch is below the plane's width", i);
     }
+    // under 16 bits: the conversions around the filter, plane i of the caller -> intermediate and intermediate -> plane i (pointers per group)
+    std::vector<vszip_depth_plane> up, down;
+    std::vector<vszip_plane> mid;
+    if (low) {
+        up.resize(nplanes), down.resize(nplanes), mid.resize(nplanes);
+        for (int i = 0; i < nplanes; ++i) {
+            const vszip_plane &s = planes[i];
+            const ptrdiff_t pitch = ((ptrdiff_t)s.w + 7) & ~(ptrdiff_t)7;  // whole 16-byte groups
+            up[i] = vszip_depth_plane{s.src, s.src_stride, nullptr, pitch, s.w, s.h, 0};
+            down[i] = vszip_depth_plane{nullptr, pitch, s.dst, s.dst_stride, s.w, s.h, 0};
+            mid[i] = vszip_plane{};
+            mid[i].src_stride = mid[i].dst_stride = pitch;
+            mid[i].w = s.w, mid[i].h = s.h;
+        }
+        char msg[256];
+        // the conversions' own checks (the caller's pitches), with a stand-in for the intermediates that do not exist yet
+        for (int i = 0; i < nplanes; ++i) up[i].dst = msg, down[i].src = msg;
+        int bad = vszip_depth_check(low->bits, 16, 0, low->full_range, up.data(), nplanes, msg, sizeof msg);
+        if (bad == VSZIP_OK) bad = vszip_depth_check(16, low->bits, 1, low->full_range, down.data(), nplanes, msg, sizeof msg);
+        if (bad != VSZIP_OK) return vszip_set_error(ctx, bad, "%s", msg);
+        planes = nullptr;  // from here on: up / mid / down
+    }
     VSZIP_HIP_CHECK(ctx, hipSetDevice(ctx->device));
 
     // the gather path: 0 by max_offset, 1 the LDS tile wherever its halo covers max_offset, 2 always global memory
@@ -128,8 +153,10 @@ VSZIP_EXPORT int vszip_deband(vszip_ctx *ctx, int dtype, const vszip_plane *plan
     int halo = 0;
     if (path != 2 && max_offset <= kHaloLarge) halo = max_offset <= kHaloSmall ? kHaloSmall : kHaloLarge;
 
-    // mode 7: plane groups whose angle planes fit the scratch cap (a plane alone may exceed it: planes are never split)
-    const size_t cap = (size_t)std::max(ctx->opt.deband_scratch_mib, 1) << 20;
+    // plane groups whose scratch fits the caps (a plane alone may exceed them: planes are never split). Mode 7: the angle planes, at most
+    // VSZIP_DEBAND_SCRATCH_MIB. Under 16 bits: two intermediates a plane, at most VSZIP_DEBAND_LOWBIT_SCRATCH_MIB, and the carry rows of the
+    // conversion back.
+    const size_t cap = (size_t)std::max(ctx->opt.deband_scratch_mib, 1) << 20, cap_low = (size_t)std::max(ctx->opt.deband_lowbit_scratch_mib, 1) << 20;
     DebParams prm;
     prm.angle_boost = angle_boost;
     prm.max_angle = max_angle;
@@ -138,26 +165,55 @@ VSZIP_EXPORT int vszip_deband(vszip_ctx *ctx, int dtype, const vszip_plane *plan
         int n = nplanes - done;
         scratch::Layout lay;
         std::vector<scratch::Region<float>> angle;  // the group's angle planes, a multiple of 256 bytes each
+        std::vector<scratch::Region<uint16_t>> inter;  // the group's intermediates, two a plane
+        std::vector<scratch::Region<float>> carry;
         char *base = nullptr;
-        if (sample_mode == 7) {
+        if (sample_mode == 7 || low) {
             n = 0;
+            size_t angle_bytes = 0, inter_bytes = 0;
             while (done + n < nplanes) {
+                const int w = low ? mid[done + n].w : planes[done + n].w, h = low ? mid[done + n].h : planes[done + n].h;
                 scratch::Layout with = lay;
-                const scratch::Region<float> a = with.take<float>((size_t)planes[done + n].w * planes[done + n].h);
-                with.align_to(256);
-                if (n > 0 && with.bytes() > cap) break;
+                scratch::Region<float> a;
+                scratch::Region<uint16_t> ia, ib;
+                size_t angle_with = angle_bytes, inter_with = inter_bytes;
+                if (sample_mode == 7) {
+                    a = with.take<float>((size_t)w * h);
+                    with.align_to(256);
+                    angle_with = (angle_bytes + a.bytes() + 255) / 256 * 256;
+                }
+                if (low) {
+                    const size_t count = (size_t)mid[done + n].src_stride * h;
+                    ia = with.take<uint16_t>(count, 256);
+                    ib = with.take<uint16_t>(count, 256);
+                    with.align_to(256);
+                    inter_with += 2 * ((ia.bytes() + 255) / 256 * 256);
+                }
+                if (n > 0 && ((sample_mode == 7 && angle_with > cap) || (low && inter_with > cap_low))) break;
                 lay = with;
-                angle.push_back(a);
+                angle_bytes = angle_with, inter_bytes = inter_with;
+                if (sample_mode == 7) angle.push_back(a);
+                if (low) inter.push_back(ia), inter.push_back(ib);
                 ++n;
             }
+            if (low) vszip_depth_take_carry(ctx, lay, down.data() + done, n, 1, carry);
             const int rc = vszip_reserve_scratch(ctx, lay, &base);
             if (rc != VSZIP_OK) return rc;
         }
+        if (low) {
+            for (int j = 0; j < n; ++j) {
+                uint16_t *a = inter[2 * j].in(base), *b = inter[2 * j + 1].in(base);
+                up[done + j].dst = a, mid[done + j].src = a, mid[done + j].dst = b, down[done + j].src = b;
+            }
+            const int rc = vszip_depth_queue(ctx, up.data() + done, n, low->bits, 16, 0, low->full_range, std::vector<scratch::Region<float>>(n), base);
+            if (rc != VSZIP_OK) return rc;
+        }
+        const vszip_plane *group = low ? mid.data() : planes;
         const int rc = vszip_for_each_table(
             ctx, prm, n,
             [&](DebPlane &d, int j) -> int {
                 const int i = done + j;
-                const vszip_plane &s = planes[i];
+                const vszip_plane &s = group[i];
                 const vszip_deband_plane &q = per[i];
                 d.src = s.src;
                 d.dst = s.dst;
@@ -190,7 +246,27 @@ VSZIP_EXPORT int vszip_deband(vszip_ctx *ctx, int dtype, const vszip_plane *plan
                 return VSZIP_OK;
             });
         if (rc != VSZIP_OK) return rc;
+        if (low) {
+            const int rc2 = vszip_depth_queue(ctx, down.data() + done, n, 16, low->bits, 1, low->full_range, carry, base);
+            if (rc2 != VSZIP_OK) return rc2;
+        }
         done += n;
     }
     return VSZIP_OK;
+}
+
+}  // namespace
+
+VSZIP_EXPORT int vszip_deband(vszip_ctx *ctx, int dtype, const vszip_plane *planes, const vszip_deband_plane *per, int nplanes, int sample_mode, int blur_first,
+                              float angle_boost, float max_angle, int max_offset) {
+    if (!ctx) return VSZIP_ERR_ARG;
+    return deband_run(ctx, dtype, planes, per, nplanes, sample_mode, blur_first, angle_boost, max_angle, max_offset, nullptr);
+}
+
+VSZIP_EXPORT int vszip_deband_lowbit(vszip_ctx *ctx, int bits, int full_range, const vszip_plane *planes, const vszip_deband_plane *per, int nplanes, int sample_mode,
+                                     int blur_first, float angle_boost, float max_angle, int max_offset) {
+    if (!ctx) return VSZIP_ERR_ARG;
+    if (bits < 8 || bits > 15) return vszip_set_error(ctx, VSZIP_ERR_ARG, "Deband: bits %d is outside 8..15 (16-bit clips go through vszip_deband)", bits);
+    const LowBit low{bits, full_range};
+    return deband_run(ctx, VSZIP_U16, planes, per, nplanes, sample_mode, blur_first, angle_boost, max_angle, max_offset, &low);
 }

@@ -646,3 +646,28 @@ VSZIP_EXPORT int vszip_color_map_lut(const float *r, const float *g, const float
     }
     return VSZIP_OK;
 }
+
+// ---- Depth: the argument checks of vszip_depth, in its order (tests/depth_ref.py check_args restates them) ----
+VSZIP_EXPORT int vszip_depth_check(int bits_in, int bits_out, int dither, int full_range, const vszip_depth_plane *planes, int nplanes, char *err, size_t err_cap) {
+    char none[1];
+    if (!err || !err_cap) err = none, err_cap = sizeof none;
+    err[0] = 0;
+    auto fail = [](int code, int) { return code; };
+    if (bits_in < 8 || bits_in > 16) return fail(VSZIP_ERR_ARG, std::snprintf(err, err_cap, "Depth: bits_in %d is outside 8..16", bits_in));
+    if (bits_out < 8 || bits_out > 16) return fail(VSZIP_ERR_ARG, std::snprintf(err, err_cap, "Depth: bits_out %d is outside 8..16", bits_out));
+    if (dither != 0 && dither != 1) return fail(VSZIP_ERR_ARG, std::snprintf(err, err_cap, "Depth: dither %d is neither 0 (none) nor 1 (error diffusion)", dither));
+    if (!planes || nplanes <= 0) return fail(VSZIP_ERR_ARG, std::snprintf(err, err_cap, "Depth: no planes"));
+    long long rows = 0;
+    for (int i = 0; i < nplanes; ++i) {
+        const vszip_depth_plane &s = planes[i];
+        if (!s.src || !s.dst) return fail(VSZIP_ERR_ARG, std::snprintf(err, err_cap, "Depth: plane %d: src and dst must not be NULL", i));
+        if (s.w < 1 || s.h < 1 || s.src_stride < s.w || s.dst_stride < s.w || std::max(s.src_stride, s.dst_stride) > 2147483647)
+            return fail(VSZIP_ERR_ARG, std::snprintf(err, err_cap, "Depth: plane %d: bad geometry %dx%d, pitches %lld -> %lld", i, (int)s.w, (int)s.h, (long long)s.src_stride,
+                                                     (long long)s.dst_stride));
+        if (full_range && s.chroma)
+            return fail(VSZIP_ERR_UNSUPPORTED, std::snprintf(err, err_cap, "Depth: plane %d: full-range chroma is not built (DESIGN.md section 1)", i));
+        rows += s.h;
+    }
+    if (rows > 2147483647 / 2) return fail(VSZIP_ERR_UNSUPPORTED, std::snprintf(err, err_cap, "Depth: %lld rows are more than one call numbers", rows));
+    return VSZIP_OK;
+}

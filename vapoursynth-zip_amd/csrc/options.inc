@@ -19,6 +19,7 @@ VSZIP_OPT(placement_tries, "VSZIP_PLACEMENT_TRIES", 24)         // ... looking a
 VSZIP_OPT(placement_budget_ms, "VSZIP_PLACEMENT_BUDGET_MS", 300)  // ... and never starting another candidate after this many milliseconds of search
 VSZIP_OPT(clahe_scratch_mib, "VSZIP_CLAHE_SCRATCH_MIB", 1024)  // CLAHE: histogram + LUT storage of one plane group at most (a larger table runs in several groups; a plane is never split)
 VSZIP_OPT(deband_scratch_mib, "VSZIP_DEBAND_SCRATCH_MIB", 1024)  // Deband sample mode 7: gradient-angle planes of one plane group at most (a larger table runs in several groups; a plane is never split)
+VSZIP_OPT(deband_lowbit_scratch_mib, "VSZIP_DEBAND_LOWBIT_SCRATCH_MIB", 1024)  // Deband under 16 bits: the two 16-bit intermediates of one plane group at most (a larger table runs in several groups; a plane is never split)
 
 // ---- path selectors between shipped kernels ----
 VSZIP_OPT(scan_mode, "VSZIP_SCAN_MODE", 0)                // BoxBlur CT: 0 ring kernel, 1 generic kernel + shuffle scan, 2 generic kernel + DPP scan
@@ -39,6 +40,7 @@ VSZIP_OPT(minmax_no_predict, "VSZIP_MINMAX_NO_PREDICT", 0)   // thresholded Plan
 VSZIP_OPT(ssim_no_yuv420_lds, "VSZIP_SSIM_NO_YUV420_LDS", 0)  // SSIMULACRA2 on 4:2:0 / 4:2:2 / 4:4:4 integer clips: the fused tile kernel (what the other YUV formats take) instead of the persistent pre-stage passes with the transfer table in LDS + the f32 pyramid pass (rounds 5, 6)
 VSZIP_OPT(deband_path, "VSZIP_DEBAND_PATH", 0)            // Deband gathers: 0 by the call's max_offset (LDS tile up to 32, else global memory), 1 the LDS tile wherever its halo covers max_offset, 2 always global memory
 VSZIP_OPT(bilateral_dither_path, "VSZIP_BILATERAL_DITHER_PATH", 0)  // BilateralDither taps: 0 the LDS tile where tile + halo (+ ref tile) fit its LDS budget, else global memory; 1 the LDS tile wherever it fits; 2 always global memory
+VSZIP_OPT(depth_waves, "VSZIP_DEPTH_WAVES", 0)            // Depth error diffusion: 0 the workgroup by the plane's rows (4 waves up to 256 rows, else 16), 4 | 16 that workgroup for every plane
 
 // ---- development variants (measured losers and sweep knobs) ----
 // (round 5: selectors whose alternative is never the faster one on any geometry of tools/cliff_sweep.py; the kernels that geometry rules still route to stay in the default build, only the switch that FORCES them is a development variant)
