@@ -451,6 +451,40 @@ int vszip_deband_lowbit(vszip_ctx *ctx, int bits, int full_range, const vszip_pl
                         int sample_mode, int blur_first, float angle_boost, float max_angle, int max_offset);
 
 /*
+ * DepthFmt — the change of sample type that resize.Point(format=...) makes on the host: between integer (VSZIP_U8 with bits 8, VSZIP_U16
+ * with bits 9..16), half (VSZIP_F16, bits 16) and float (VSZIP_F32, bits 32) planes, as zimg does it (oracle/vs_host.py int_to_float /
+ * float_to_int restate it; the reference's float and YUV goldens pass through those). What a caller with 8-bit frames needs around
+ * vszip_eedi3 and the float paths of the other filters, and what the display path needs before vszip_pack_rgb. The plane struct is
+ * vszip_depth_plane: src a plane of dtype_in, dst one of dtype_out, strides in elements of each plane's own sample type, `chroma` as for
+ * vszip_depth. Any number of planes of any mix of sizes in one call, w, h >= 1. full_range describes the integer side; float <-> float
+ * ignores it. IEEE f32 throughout. With
+ *   limited range   off = (chroma ? 128 : 16) << (bits - 8),  rng = (chroma ? 224 : 219) << (bits - 8)
+ *   full range      off = chroma ? 2^(bits - 1) : 0,          rng = 2^bits - 1
+ *   int -> f32, dither 0    fmaf((float)v, f32(1.0 / rng), f32(-off / rng)): both constants divided in double and rounded once, ONE fused
+ *           operation (the plain product when off is 0). All four range / chroma cases.
+ *   f32 -> int, dither 0    q = rint(fmaf(x, (float)rng, (float)off)), half to even, clamped to [0, 2^bits - 1]. All four cases. +-Inf clamp;
+ *           NaN is outside the contract.
+ *   f32 -> int, dither 1    error diffusion where off is 0 (full range, chroma 0: RGBS, full-range gray or luma): vszip_depth's
+ *           recurrence on src = the float sample with scale = (float)rng, the product rounded on its own. With an offset (limited range,
+ *           or chroma) VSZIP_ERR_UNSUPPORTED: no recorded data pins whether zimg adds it fused (as for full-range chroma in vszip_depth).
+ *   f16 -> f32 is exact; f32 -> f16 rounds to nearest even, subnormals kept, overflow to Inf.
+ *   int <-> f16   as f32: the f32 result rounded to f16; the f16 sample widened, then the f32 rule. (No golden reaches half planes.)
+ *   int -> int    vszip_depth itself, results and errors.
+ * One streaming pass (a lane owns 16 bytes of the narrower plane), or vszip_depth's wavefront for the error diffusion, with its scratch
+ * rule. Asynchronous on the context stream; "plane memory" as for vszip_depth: reads stay inside [0, w) x h of src, only [0, w) x h of
+ * dst is written, dst overlaps no src. vszip_depth_fmt_check (device-free) is the argument check made first, text in `err` (may be NULL):
+ * VSZIP_ERR_ARG for a dtype outside the four ("DepthFmt: dtype_in 4 is none of VSZIP_U8, VSZIP_U16, VSZIP_F16, VSZIP_F32"), bits that do
+ * not fit the dtype ("DepthFmt: bits_in 8 does not fit VSZIP_U16 (9..16)"), a dither other than 0 or 1, dither 1 with a float destination
+ * ("DepthFmt: error diffusion needs an integer destination, dtype_out is VSZIP_F32"), no planes, and, naming the plane, a NULL plane, w or
+ * h below 1, a pitch below w; VSZIP_ERR_UNSUPPORTED for float -> integer error diffusion with an offset. Two integer dtypes: after the
+ * dtype and bits checks, vszip_depth_check's codes and texts ("Depth: ...").
+ */
+int vszip_depth_fmt_check(int dtype_in, int bits_in, int dtype_out, int bits_out, int dither, int full_range, const vszip_depth_plane *planes,
+                          int nplanes, char *err, size_t err_cap);
+int vszip_depth_fmt(vszip_ctx *ctx, const vszip_depth_plane *planes, int nplanes, int dtype_in, int bits_in, int dtype_out, int bits_out,
+                    int dither, int full_range);
+
+/*
  * BilateralDither — the port of dither's Dither_bilateral16: replaces processPlane of src/filters/bilateral_dither.zig:34-213
  * as called per plane by GetFrame(T).gf (src/vapoursynth/bilateral_dither.zig:52-110), the per-plane derivation of its create
  * function (:151-209 with buildSlot :40-50) and generate of src/filters/bilateral_dither_subspl.zig:245-361.

@@ -27,7 +27,8 @@ FLAGS = [
 # and pays for the pairs with register copies (measured: +1.7 % with it off, profiles/r04_notes.md section 10)
 # limit_filter: the vector-combine pass turns the 8-bit kernel's 16-byte loads into byte loads (their lanes are only extracted), and those lose
 # the non-temporal hint before the backend merges them back into 16-byte loads (tests/test_stream_cache_hints.py)
-FILE_FLAGS = {"eedi3": ["-fno-slp-vectorize"], "limit_filter": ["-mllvm", "-disable-vector-combine"]}
+# depth_fmt: the same for the 8-byte loads of its u8 -> f32 kernel (tests/test_depth_fmt_isa.py)
+FILE_FLAGS = {"eedi3": ["-fno-slp-vectorize"], "limit_filter": ["-mllvm", "-disable-vector-combine"], "depth_fmt": ["-mllvm", "-disable-vector-combine"]}
 
 
 def _stale(out: Path, deps) -> bool:

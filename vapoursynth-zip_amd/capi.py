@@ -278,6 +278,8 @@ SYMBOLS = {
     "vszip_deband": (_i, [_vp, _i, _PP, C.POINTER(DebandPlane), _i, _i, _i, C.c_float, C.c_float, _i]),
     "vszip_depth_check": (_i, [_i, _i, _i, _i, C.POINTER(DepthPlane), _i, C.c_char_p, _sz]),
     "vszip_depth": (_i, [_vp, C.POINTER(DepthPlane), _i, _i, _i, _i, _i]),
+    "vszip_depth_fmt_check": (_i, [_i, _i, _i, _i, _i, _i, C.POINTER(DepthPlane), _i, C.c_char_p, _sz]),
+    "vszip_depth_fmt": (_i, [_vp, C.POINTER(DepthPlane), _i, _i, _i, _i, _i, _i, _i]),
     "vszip_deband_lowbit": (_i, [_vp, _i, _i, _PP, C.POINTER(DebandPlane), _i, _i, _i, C.c_float, C.c_float, _i]),
     "vszip_bilateral_dither_derive": (_i, [_i, _i, _i, C.c_float, C.c_float, C.c_float, C.c_float, C.POINTER(BilateralDitherCfg), C.c_char_p, _sz]),
     "vszip_bilateral_dither_points": (_i, [_i, C.c_float, _vp, _sz, C.POINTER(C.c_int32)]),
@@ -314,6 +316,17 @@ def depth_check(bits_in, bits_out, dither, full_range, planes) -> None:
     arr = (DepthPlane * max(n, 1))(*[DepthPlane(*p) for p in planes])
     err = C.create_string_buffer(256)
     rc = load().vszip_depth_check(int(bits_in), int(bits_out), int(dither), int(full_range), arr if n else None, n, err, len(err))
+    if rc != 0:
+        raise VszipError(rc, err.value.decode())
+
+
+def depth_fmt_check(dtype_in, bits_in, dtype_out, bits_out, dither, full_range, planes) -> None:
+    """vszip_depth_fmt_check (device-free): the argument checks of vszip_depth_fmt; dtypes U8 / U16 / F16 / F32, planes as for depth_check.
+    VszipError with the library's code and text."""
+    n = len(planes)
+    arr = (DepthPlane * max(n, 1))(*[DepthPlane(*p) for p in planes])
+    err = C.create_string_buffer(256)
+    rc = load().vszip_depth_fmt_check(int(dtype_in), int(bits_in), int(dtype_out), int(bits_out), int(dither), int(full_range), arr if n else None, n, err, len(err))
     if rc != 0:
         raise VszipError(rc, err.value.decode())
 
@@ -985,6 +998,33 @@ class Device:
     def prepared_depth(self, srcs, dsts, bits_in, bits_out, dither=DITHER_NONE, full_range=False, chroma=None):
         """-> a callable queueing vszip_depth on argument blocks built once."""
         fn, ctx, check, args = self.lib.vszip_depth, self.ctx, self.check, self._depth_args(srcs, dsts, bits_in, bits_out, dither, full_range, chroma)
+        return lambda: check(fn(ctx, *args))
+
+    def _depth_fmt_args(self, srcs, dsts, dtype_in, bits_in, dtype_out, bits_out, dither, full_range, chroma):
+        n = len(srcs)
+        ch = [int(bool(chroma))] * n if chroma is None or np.isscalar(chroma) else [int(bool(c)) for c in chroma]
+        if len(dsts) != n or len(ch) != n:
+            raise ValueError("depth_fmt: one destination (and one chroma flag) per plane")
+        for name, ps, dt in (("source", srcs, dtype_in), ("destination", dsts, dtype_out)):
+            if int(dt) in (U8, U16, F16, F32) and any(p.dtype != _DT2NP[int(dt)] for p in ps):
+                raise ValueError(f"depth_fmt: {name} planes are {_DT2NP[int(dt)].name}")
+        if any((s.w, s.h) != (d.w, d.h) for s, d in zip(srcs, dsts)):
+            raise ValueError("depth_fmt: a destination has its source's size")
+        arr = (DepthPlane * n)()
+        for i in range(n):
+            arr[i] = DepthPlane(srcs[i].ptr, srcs[i].stride, dsts[i].ptr, dsts[i].stride, srcs[i].w, srcs[i].h, ch[i])
+        return (arr, n, int(dtype_in), int(bits_in), int(dtype_out), int(bits_out), int(dither), int(bool(full_range)))
+
+    def depth_fmt(self, srcs, dsts, dtype_in, bits_in, dtype_out, bits_out, dither=DITHER_NONE, full_range=False, chroma=None):
+        """vszip_depth_fmt on every plane: srcs of dtype_in / bits_in, dsts of dtype_out / bits_out (U8: 8, U16: 9..16, F16: 16, F32: 32), any mix of
+        sizes; full_range describes the integer side; chroma a scalar or one flag per plane. Error diffusion (DITHER_ERROR_DIFFUSION) to integers
+        from float planes is served at full range, non-chroma (VSZIP_ERR_UNSUPPORTED otherwise). dsts overlap no source."""
+        self.check(self.lib.vszip_depth_fmt(self.ctx, *self._depth_fmt_args(srcs, dsts, dtype_in, bits_in, dtype_out, bits_out, dither, full_range, chroma)))
+
+    def prepared_depth_fmt(self, srcs, dsts, dtype_in, bits_in, dtype_out, bits_out, dither=DITHER_NONE, full_range=False, chroma=None):
+        """-> a callable queueing vszip_depth_fmt on argument blocks built once."""
+        fn, ctx, check = self.lib.vszip_depth_fmt, self.ctx, self.check
+        args = self._depth_fmt_args(srcs, dsts, dtype_in, bits_in, dtype_out, bits_out, dither, full_range, chroma)
         return lambda: check(fn(ctx, *args))
 
     def upload_bilateral_dither_points(self, pts: np.ndarray) -> DevPlane:

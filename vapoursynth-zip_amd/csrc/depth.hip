@@ -76,6 +76,27 @@ __global__ __launch_bounds__(kRowUnitThreads) void depth_none_kernel(const Depth
 }
 
 // ---- error diffusion ------------------------------------------------------------------------------------------------------------------
+// A sample as the bits a Group keeps, and those bits as the f32 the arithmetic starts from: integers by value, float planes (the
+// instantiations of depth_fmt.hip: f32, and f16 widened at pop) by their bit pattern.
+template <typename T>
+__device__ __forceinline__ uint32_t sample_bits(T v) {
+    if constexpr (std::is_integral_v<T>)
+        return (uint32_t)v;
+    else if constexpr (sizeof(T) == 4)
+        return __float_as_uint(v);
+    else
+        return (uint32_t)__builtin_bit_cast(uint16_t, v);
+}
+template <typename T>
+__device__ __forceinline__ float sample_value(uint32_t bits) {
+    if constexpr (std::is_integral_v<T>)
+        return (float)bits;
+    else if constexpr (sizeof(T) == 4)
+        return __uint_as_float(bits);
+    else
+        return (float)__builtin_bit_cast(T, (uint16_t)bits);
+}
+
 // Eight samples of T as a shift register of dwords: pop() takes the lowest sample, push() enters one at the top (after eight the group
 // is in memory order).
 template <typename T>
@@ -87,13 +108,21 @@ struct Group {
         for (int k = 0; k < N; ++k) r[k] = 0;
     }
     __device__ __forceinline__ uint32_t pop() {
-        const uint32_t s = r[0] & ((1u << B) - 1u);
+        if constexpr (B == 32) {  // a sample a dword: the registers move up whole
+            const uint32_t s = r[0];
 #pragma unroll
-        for (int k = 0; k + 1 < N; ++k) r[k] = (r[k] >> B) | (r[k + 1] << (32 - B));
-        r[N - 1] >>= B;
-        return s;
+            for (int k = 0; k + 1 < N; ++k) r[k] = r[k + 1];
+            return s;
+        } else {
+            const uint32_t s = r[0] & ((1u << B) - 1u);
+#pragma unroll
+            for (int k = 0; k + 1 < N; ++k) r[k] = (r[k] >> B) | (r[k + 1] << (32 - B));
+            r[N - 1] >>= B;
+            return s;
+        }
     }
     __device__ __forceinline__ void push(uint32_t q) {
+        static_assert(B < 32, "outputs are integers of 8 or 16 bits");
 #pragma unroll
         for (int k = 0; k + 1 < N; ++k) r[k] = (r[k] >> B) | (r[k + 1] << (32 - B));
         r[N - 1] = (r[N - 1] >> B) | (q << (32 - B));
@@ -104,20 +133,24 @@ struct Group {
             if constexpr (N == 2) {
                 const u32x2 v = *reinterpret_cast<const u32x2 *>(row + x0);
                 r[0] = v.x, r[1] = v.y;
-            } else {
+            } else if constexpr (N == 4) {
                 const u32x4 v = *reinterpret_cast<const u32x4 *>(row + x0);
                 r[0] = v.x, r[1] = v.y, r[2] = v.z, r[3] = v.w;
+            } else {  // 32-bit samples: two 16-byte loads
+                const u32x4 a = *reinterpret_cast<const u32x4 *>(row + x0), b = *(reinterpret_cast<const u32x4 *>(row + x0) + 1);
+                r[0] = a.x, r[1] = a.y, r[2] = a.z, r[3] = a.w, r[4] = b.x, r[5] = b.y, r[6] = b.z, r[7] = b.w;
             }
         } else {
             clear();
 #pragma unroll
             for (int j = 0; j < dp::kGroup; ++j)
-                if (x0 + j < w) r[j * B / 32] |= (uint32_t)row[x0 + j] << (j * B % 32);
+                if (x0 + j < w) r[j * B / 32] |= sample_bits(row[x0 + j]) << (j * B % 32);
         }
     }
     // the n samples pushed last to [x0, x0 + n) of a row
     __device__ __forceinline__ void store(T *row, int x0, int n, bool vec) {
         if (vec && n == dp::kGroup) {
+            static_assert(N <= 4, "outputs are integers of 8 or 16 bits");
             if constexpr (N == 2) {
                 u32x2 v;
                 v.x = r[0], v.y = r[1];
@@ -196,7 +229,7 @@ __global__ __launch_bounds__(WAVES * dp::kLanes) void depth_diffuse_kernel(const
                         cur = next;
                         if (x + dp::kGroup < w) next.load(srow, x + dp::kGroup, w, svec);
                     }
-                    const float q = dp::diffuse((float)cur.pop(), scale, peak, e, top_m1, top_0, top_p1, &en);
+                    const float q = dp::diffuse(sample_value<Tin>(cur.pop()), scale, peak, e, top_m1, top_0, top_p1, &en);
                     out.push((uint32_t)q);
                     if ((x & (dp::kGroup - 1)) == dp::kGroup - 1 || x == w - 1) out.store(drow, x & ~(dp::kGroup - 1), (x & (dp::kGroup - 1)) + 1, dvec);
                     if (lane == dp::kLanes - 1) {
@@ -232,6 +265,22 @@ void launch_diffuse(vszip_ctx *ctx, int waves, int blocks, const DepthParams &t)
 
 bool aligned16(const void *p, ptrdiff_t stride, size_t size) { return ((reinterpret_cast<uintptr_t>(p) | (uintptr_t)((size_t)stride * size)) & 15) == 0; }
 
+// one plane's entry
+template <typename Tin, typename Tout>
+void depth_fill(DepthPlane &d, const vszip_depth_plane &s, float *carry) {
+    d.src = s.src;
+    d.dst = s.dst;
+    d.carry = carry;
+    d.sstride = (int)s.src_stride;
+    d.dstride = (int)s.dst_stride;
+    d.w = s.w;
+    d.h = s.h;
+    d.svec = aligned16(s.src, s.src_stride, sizeof(Tin));
+    d.dvec = aligned16(s.dst, s.dst_stride, sizeof(Tout));
+    constexpr int V = (sizeof(Tin) == 1 || sizeof(Tout) == 1) ? 16 : 8;
+    d.rows = (short)vszip_rows_per_workgroup(d.svec && d.dvec ? s.w / V : s.w);
+}
+
 // the planes `idx` of the table through one kernel: waves 0 none, else the error-diffusion workgroup
 template <typename Tin, typename Tout>
 int depth_run(vszip_ctx *ctx, const vszip_depth_plane *planes, const std::vector<int> &idx, int waves, DepthParams &prm,
@@ -240,19 +289,8 @@ int depth_run(vszip_ctx *ctx, const vszip_depth_plane *planes, const std::vector
         ctx, prm, (int)idx.size(),
         [&](DepthPlane &d, int j) -> int {
             const int i = idx[j];
-            const vszip_depth_plane &s = planes[i];
-            d.src = s.src;
-            d.dst = s.dst;
-            d.carry = carry[i].count ? carry[i].in(base) : nullptr;
-            d.sstride = (int)s.src_stride;
-            d.dstride = (int)s.dst_stride;
-            d.w = s.w;
-            d.h = s.h;
-            d.svec = aligned16(s.src, s.src_stride, sizeof(Tin));
-            d.dvec = aligned16(s.dst, s.dst_stride, sizeof(Tout));
-            constexpr int V = (sizeof(Tin) == 1 || sizeof(Tout) == 1) ? 16 : 8;
-            d.rows = (short)vszip_rows_per_workgroup(d.svec && d.dvec ? s.w / V : s.w);
-            return waves ? 1 : (s.h + d.rows - 1) / d.rows;
+            depth_fill<Tin, Tout>(d, planes[i], carry[i].count ? carry[i].in(base) : nullptr);
+            return waves ? 1 : (planes[i].h + d.rows - 1) / d.rows;
         },
         [&](const DepthParams &t, int blocks, int) {
             vszip_probe_scope probe(ctx);
@@ -266,6 +304,7 @@ int depth_run(vszip_ctx *ctx, const vszip_depth_plane *planes, const std::vector
 
 }  // namespace
 
+#ifndef VSZIP_DEPTH_KERNELS_ONLY  // depth_fmt.hip instantiates the kernels above for float sources; the entry points are built once, here
 int vszip_depth_waves(const vszip_ctx *ctx, int h) {
     const int forced = ctx->opt.depth_waves;
     return forced == dp::kWavesSmall || forced == dp::kWavesLarge ? forced : dp::waves_for(h);
@@ -316,3 +355,4 @@ VSZIP_EXPORT int vszip_depth(vszip_ctx *ctx, const vszip_depth_plane *planes, in
     }
     return vszip_depth_queue(ctx, planes, nplanes, bits_in, bits_out, dither, full_range, carry, base);
 }
+#endif  // VSZIP_DEPTH_KERNELS_ONLY

@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../../include/vszip_hip.h"
+#include "depth_fmt.hpp"
 
 #define VSZIP_EXPORT extern "C" __attribute__((visibility("default")))
 
@@ -669,5 +670,48 @@ VSZIP_EXPORT int vszip_depth_check(int bits_in, int bits_out, int dither, int fu
         rows += s.h;
     }
     if (rows > 2147483647 / 2) return fail(VSZIP_ERR_UNSUPPORTED, std::snprintf(err, err_cap, "Depth: %lld rows are more than one call numbers", rows));
+    return VSZIP_OK;
+}
+
+// ---- DepthFmt: the argument checks of vszip_depth_fmt, in its order (tests/depth_fmt_ref.py check_args restates them) ----
+VSZIP_EXPORT int vszip_depth_fmt_check(int dtype_in, int bits_in, int dtype_out, int bits_out, int dither, int full_range, const vszip_depth_plane *planes,
+                                       int nplanes, char *err, size_t err_cap) {
+    namespace df = depth_fmt;
+    char none[1];
+    if (!err || !err_cap) err = none, err_cap = sizeof none;
+    err[0] = 0;
+    auto fail = [](int code, int) { return code; };
+    const struct {
+        const char *name;
+        int dtype, bits;
+    } side[2] = {{"in", dtype_in, bits_in}, {"out", dtype_out, bits_out}};
+    for (const auto &s : side)
+        if (!df::known_dtype(s.dtype))
+            return fail(VSZIP_ERR_ARG, std::snprintf(err, err_cap, "DepthFmt: dtype_%s %d is none of VSZIP_U8, VSZIP_U16, VSZIP_F16, VSZIP_F32", s.name, s.dtype));
+    for (const auto &s : side)
+        if (!df::bits_fit(s.dtype, s.bits)) {
+            const int lo = df::bits_lo(s.dtype), hi = df::bits_hi(s.dtype);
+            if (lo == hi) return fail(VSZIP_ERR_ARG, std::snprintf(err, err_cap, "DepthFmt: bits_%s %d does not fit %s (%d)", s.name, s.bits, df::dtype_name(s.dtype), lo));
+            return fail(VSZIP_ERR_ARG, std::snprintf(err, err_cap, "DepthFmt: bits_%s %d does not fit %s (%d..%d)", s.name, s.bits, df::dtype_name(s.dtype), lo, hi));
+        }
+    const bool in_float = df::is_float(dtype_in), out_float = df::is_float(dtype_out);
+    if (!in_float && !out_float) return vszip_depth_check(bits_in, bits_out, dither, full_range, planes, nplanes, err, err_cap);  // vszip_depth itself
+    if (dither != 0 && dither != 1) return fail(VSZIP_ERR_ARG, std::snprintf(err, err_cap, "DepthFmt: dither %d is neither 0 (none) nor 1 (error diffusion)", dither));
+    if (dither && out_float)
+        return fail(VSZIP_ERR_ARG, std::snprintf(err, err_cap, "DepthFmt: error diffusion needs an integer destination, dtype_out is %s", df::dtype_name(dtype_out)));
+    if (!planes || nplanes <= 0) return fail(VSZIP_ERR_ARG, std::snprintf(err, err_cap, "DepthFmt: no planes"));
+    long long rows = 0;
+    for (int i = 0; i < nplanes; ++i) {
+        const vszip_depth_plane &s = planes[i];
+        if (!s.src || !s.dst) return fail(VSZIP_ERR_ARG, std::snprintf(err, err_cap, "DepthFmt: plane %d: src and dst must not be NULL", i));
+        if (s.w < 1 || s.h < 1 || s.src_stride < s.w || s.dst_stride < s.w || std::max(s.src_stride, s.dst_stride) > 2147483647)
+            return fail(VSZIP_ERR_ARG, std::snprintf(err, err_cap, "DepthFmt: plane %d: bad geometry %dx%d, pitches %lld -> %lld", i, (int)s.w, (int)s.h,
+                                                     (long long)s.src_stride, (long long)s.dst_stride));
+        if (dither && df::range_of(bits_out, full_range != 0, s.chroma != 0).off != 0)
+            return fail(VSZIP_ERR_UNSUPPORTED, std::snprintf(err, err_cap, "DepthFmt: plane %d: error diffusion from float with an offset (%s) is not built (DESIGN.md section 1)", i,
+                                                             full_range ? "chroma" : "limited range"));
+        rows += s.h;
+    }
+    if (rows > 2147483647 / 2) return fail(VSZIP_ERR_UNSUPPORTED, std::snprintf(err, err_cap, "DepthFmt: %lld rows are more than one call numbers", rows));
     return VSZIP_OK;
 }
